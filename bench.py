@@ -24,6 +24,12 @@ F.linear, fp32) on the host cores, a bounded sample, rank 0 / N=1 only (kind "re
 CPU GEMM, this library call IS its inference op).  `ldlq_cpu_reference`: the reference's own bal.py / vector_balance.py
 (staged copies, oracle/ref_ldlq_time.py in a subprocess) timed on the same host cores; `ldlq_cpu_port`: the oracle's C
 restatement beside it.
+
+A plain run (`--gpus N --steps K --warmup W`) measures the headline alone: set-up, the pre-heat and W warm-up launches, the K timed
+cold launches, and one line with `value`, `ms_per_step`, `config` and `roofline`.  Everything else above (the parity check, `from_idle`,
+`warm`, `fp32_y`, `accumulate_contract`, `k2_shapes`, the sharded / Hessian / quantisation / decode legs and the CPU baselines) runs
+with `--full` only.  `--dump-outputs DIR` writes y of the last timed launch as DIR/y.npy (float32); the inputs are seeded, so two
+builds given the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -45,7 +51,7 @@ HBM_PEAK_GBS = 8000.0                                      # MI355X_MICROARCH.md
 MFMA_PEAK_TF = 2500.0                                      # dense bf16
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
@@ -66,7 +72,13 @@ def parse():
     ap.add_argument("--no-spin", action="store_true",
                     help="with --eager: launch without the spin kernel in front (each kernel then starts on an idle GPU: the form the "
                          "rocprofv3 passes use, whose per-kernel durations are the kernel alone)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the parity check, from_idle, warm, fp32 y, the accumulate contract, k2_shapes, the "
+                         "sharded / Hessian / quantisation / decode legs and the CPU baselines (the --no-* switches pick among them).  "
+                         "Without it a run sets up, warms up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (y [bs, m], as float32) to DIR/y.npy")
+    return ap.parse_args(argv)
 
 
 def _free_port():
@@ -161,13 +173,15 @@ def main():
     x = torch.randn(BS, D).to(torch.bfloat16).to(dev)
     y = torch.empty(BS, M, dtype=torch.bfloat16, device=dev)
 
-    # parity of the thing being timed (not timed): fp32 dense matmul of the dequantised weights
-    What = ops.codes_to_weight(codes, "b", scale, None, MAXQ, out_dtype=torch.float32)
-    y32 = ops.dequant_gemm(x, qs, BITS, "b", scale, None, None, out_dtype=torch.float32)
-    ref = x.float().double() @ What.double().T
-    rel = float((y32.double() - ref).norm() / ref.norm())
-    assert rel < 1e-3, f"parity check failed: rel err {rel}"
-    del W, What, y32, ref
+    # --full: parity of the thing being timed (not timed): fp32 dense matmul of the dequantised weights
+    if args.full:
+        What = ops.codes_to_weight(codes, "b", scale, None, MAXQ, out_dtype=torch.float32)
+        y32 = ops.dequant_gemm(x, qs, BITS, "b", scale, None, None, out_dtype=torch.float32)
+        ref = x.float().double() @ What.double().T
+        rel = float((y32.double() - ref).norm() / ref.norm())
+        assert rel < 1e-3, f"parity check failed: rel err {rel}"
+        del What, y32, ref
+    del W
 
     ring = [qs] + [qs.clone() for _ in range(max(args.ring, 1) - 1)]
     lib = _lib.load()
@@ -287,15 +301,70 @@ def main():
         return t
 
     t_idle = None
-    if args.preheat_ms > 0 and not args.profile_cold_only:
+    if args.full and args.preheat_ms > 0 and not args.profile_cold_only:
         t_idle = timed(ring, args.steps, args.warmup)                  # first: the GPU as the set-up left it (a few short launches, then idle)
     t_cold = timed(ring, args.steps, args.warmup, args.preheat_ms)
+    if args.dump_outputs and rank == 0:
+        # y as the last timed launch left it (every copy of the ring holds the same codes): what a caller of the timed path receives
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "y.npy"), y.float().cpu().numpy())
     if args.profile_cold_only:
         if rank == 0:
             emit(json.dumps({"profile_cold_only": True, "us_per_launch": t_cold / args.steps * 1e6}))
         if dist is not None:
             dist.destroy_process_group()
         return
+
+    traffic, traffic_source = None, None
+    pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "k2_pmc_latest.json")
+    if os.path.exists(pmc_path):
+        with open(pmc_path) as f:
+            pmc = json.load(f)
+        traffic = pmc.get("hbm_bytes_per_launch")
+        traffic_source = ("profiles/k2_pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command "
+                          f"(scripts/gpu_round.sh), kernel {str(pmc.get('kernel', '?'))[:60]} -- counters cannot be collected inside the timed run")
+
+    us_cold = t_cold / args.steps * 1e6
+    tf_cold = FLOPS * world / (t_cold / args.steps) / 1e12
+    gbs_cold = BYTES / (t_cold / args.steps) / 1e9         # per GPU
+    out = {
+        "metric": "2-bit dequant-GEMM TFLOP/s (4096x4096, bs=16)",
+        "value": round(tf_cold, 3),
+        "unit": "TFLOP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": us_cold * 1e-3,
+        "higher_is_better": True,
+        **({"dry_run": f"QUIP_BENCH_BACKEND={backend}: ranks share GPUs, collectives through host memory -- control flow only, the numbers mean nothing"}
+           if backend != "nccl" else {}),
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: single 4096x4096 Linear, w2 qfn-b, fused dequant-GEMM, bs=16, "
+                               f"cold weights (ring of {len(ring)} packed copies, {len(ring) * qs.numel() * 4 // 2**20} MiB; the timed launches stream copies 0..{min(len(ring), args.steps) - 1}, the warm-up ones come from the other end of the ring"
+                               + (f"; {args.preheat_ms:g} ms of the same launch on the far two thirds of the ring precede the warm-up steps (clocks at their serving state; "
+                                  "`from_idle` is the same measurement without them)" if args.preheat_ms > 0 else "") + ")", "m": M, "d": D, "bs": BS, "bits": BITS,
+                   "launch": ("eager launches queued behind a spin kernel" if (args.eager or (not args.graph and args.steps <= 256))
+                              else "one hipGraph of K launches"), "parallelism": f"dp{world} (replicas)"},
+        "roofline": {"bound": "hbm", "achieved": round(gbs_cold, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(gbs_cold / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                     "algorithmic_bytes_per_launch": BYTES, "us_per_launch": round(us_cold, 3),
+                     "pct_mfma_peak": round(100 * tf_cold / world / MFMA_PEAK_TF, 2),
+                     "regime": "achieved / frac / us_per_launch: HIP events around the K launches of THIS run, back to back from the queue"
+                               + (f", after {args.preheat_ms:g} ms of the same launch (serving clocks)" if args.preheat_ms > 0 else "")
+                               + "; traffic and the committed rocprofv3 kernel average (profiles/*_rocprof_summary.txt) come from separate passes of "
+                                 "this command with --eager --no-spin --preheat-ms 0, where every kernel starts on an idle GPU -- the regime of "
+                                 "`from_idle`, 2-5 % slower per launch than `us_per_launch`"},
+    }
+    if not args.full:                            # a plain run: the headline line and nothing else
+        if rank == 0:
+            emit(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     t_warm = timed([qs], args.steps, args.warmup, args.preheat_ms)
 
     # ---- the reference operator's own contract: y fp32, accumulated in place (quant.py:226-230) ---------------
@@ -324,51 +393,10 @@ def main():
     BYTES_F32 = M * D * BITS // 8 + 2 * BS * D + 4 * BS * M          # y written as fp32
     BYTES_ACC = M * D * BITS // 8 + 2 * BS * D + 2 * 4 * BS * M      # y read + written as fp32
 
-    traffic, traffic_source = None, None
-    pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "k2_pmc_latest.json")
-    if os.path.exists(pmc_path):
-        with open(pmc_path) as f:
-            pmc = json.load(f)
-        traffic = pmc.get("hbm_bytes_per_launch")
-        traffic_source = ("profiles/k2_pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command "
-                          f"(scripts/gpu_round.sh), kernel {str(pmc.get('kernel', '?'))[:60]} -- counters cannot be collected inside the timed run")
-
-    us_cold = t_cold / args.steps * 1e6
     us_warm = t_warm / args.steps * 1e6
-    tf_cold = FLOPS * world / (t_cold / args.steps) / 1e12
     tf_warm = FLOPS * world / (t_warm / args.steps) / 1e12
-    gbs_cold = BYTES / (t_cold / args.steps) / 1e9         # per GPU
-    out = {
-        "metric": "2-bit dequant-GEMM TFLOP/s (4096x4096, bs=16)",
-        "value": round(tf_cold, 3),
-        "unit": "TFLOP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": us_cold * 1e-3,
-        "higher_is_better": True,
-        **({"dry_run": f"QUIP_BENCH_BACKEND={backend}: ranks share GPUs, collectives through host memory -- control flow only, the numbers mean nothing"}
-           if backend != "nccl" else {}),
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: single 4096x4096 Linear, w2 qfn-b, fused dequant-GEMM, bs=16, "
-                               f"cold weights (ring of {len(ring)} packed copies, {len(ring) * qs.numel() * 4 // 2**20} MiB; the timed launches stream copies 0..{min(len(ring), args.steps) - 1}, the warm-up ones come from the other end of the ring"
-                               + (f"; {args.preheat_ms:g} ms of the same launch on the far two thirds of the ring precede the warm-up steps (clocks at their serving state; "
-                                  "`from_idle` is the same measurement without them)" if args.preheat_ms > 0 else "") + ")", "m": M, "d": D, "bs": BS, "bits": BITS,
-                   "launch": ("eager launches queued behind a spin kernel" if (args.eager or (not args.graph and args.steps <= 256))
-                              else "one hipGraph of K launches"), "parallelism": f"dp{world} (replicas)"},
+    out.update({
         "parity_rel_err": rel,
-        "roofline": {"bound": "hbm", "achieved": round(gbs_cold, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(gbs_cold / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                     "algorithmic_bytes_per_launch": BYTES, "us_per_launch": round(us_cold, 3),
-                     "pct_mfma_peak": round(100 * tf_cold / world / MFMA_PEAK_TF, 2),
-                     "regime": "achieved / frac / us_per_launch: HIP events around the K launches of THIS run, back to back from the queue"
-                               + (f", after {args.preheat_ms:g} ms of the same launch (serving clocks)" if args.preheat_ms > 0 else "")
-                               + "; traffic and the committed rocprofv3 kernel average (profiles/*_rocprof_summary.txt) come from separate passes of "
-                                 "this command with --eager --no-spin --preheat-ms 0, where every kernel starts on an idle GPU -- the regime of "
-                                 "`from_idle`, 2-5 % slower per launch than `us_per_launch`"},
         "fp32_y": {"what": "the same K launches with y written as fp32 (no accumulate): the output the parity check above holds to the north_star's "
                            "1e-3 (the bf16 y of `value` adds its own output rounding, <= 3e-3 in tests/test_gpu_dqgemm.py)",
                    "parity_rel_err": rel, "tolerance": 1e-3, "us_per_launch": round(t_f32_cold / args.steps * 1e6, 3),
@@ -389,7 +417,7 @@ def main():
             "algorithmic_bytes_per_launch": BYTES_ACC,
             "hbm_GBs": round(BYTES_ACC / (t_acc_cold / args.steps) / 1e9, 1),
             "hbm_frac": round(BYTES_ACC / (t_acc_cold / args.steps) / 1e9 / HBM_PEAK_GBS, 4)},
-    }
+    })
 
     # ---- the same kernel family on the shapes where it is a stream / a GEMM, and fp16 activations ----------
     def k2_leg(m_, d_, bs_, dt, steps):

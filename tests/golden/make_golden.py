@@ -422,9 +422,13 @@ def gen_gptq_groups():
                 arrs[f"{name}_zero"] = meth.quantizer.zero.clone()
     finally:
         torch.cuda.synchronize = sync
+    big = {k: arrs.pop(k) for k in ("H320", "H384")}              # one file holding all four Hessians would pass 1 MiB
     save("gptq_groups", "gptq.py:19-115 GPTQ.fasterquant run on CPU (torch.cuda.synchronize stubbed) after preproc(preproc_gptqH, "
          "percdamp .01), perchannel, mse off; cases (name: d, m, bits, groupsize, qfn, sym, layer) = " + repr(GPTQ_CASES) +
-         "; H<d> = the Hessian of width d before damping; per case W0 [m,d], Q = layer.weight after, error, and the quantiser left behind", **arrs)
+         "; H<d> = the Hessian of width d before damping (H320, H384: gptq_groups_hessians.npz); per case W0 [m,d], Q = layer.weight after, "
+         "error, and the quantiser left behind", **arrs)
+    save("gptq_groups_hessians", "H320 / H384 of gptq_groups.npz (the Hessians its cases of width 320 and 384 ran on), in a file of their own "
+         "so that neither file passes 1 MiB", **big)
 
 
 # ---------------------------------------------------------------- H. the reference DRIVER, end to end

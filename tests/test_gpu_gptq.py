@@ -151,6 +151,13 @@ def test_gptq_class_against_reference_golden():
 
 
 # ---- groupsize / qfn b, c (gptq.py:69-76, quant.py:10-21) against the reference's own runs -------------------------------------
+def _gptq_groups():
+    """the arrays of gptq_groups.npz with the Hessians H320 / H384 that gptq_groups_hessians.npz holds beside it"""
+    g = dict(load_golden("gptq_groups"))
+    g.update((k, v) for k, v in load_golden("gptq_groups_hessians").items() if k != "__doc__")
+    return g
+
+
 def _golden_cases():
     import ast
     doc = str(load_golden("gptq_groups")["__doc__"])
@@ -186,7 +193,7 @@ def _run_case(g, name, d, m, bits, gs, qfn, sym, layer="linear", use_kernel=True
 
 @pytest.mark.parametrize("case", range(8))
 def test_gptq_groups_and_qfn_against_reference_golden(case):
-    g = load_golden("gptq_groups")
+    g = _gptq_groups()
     name, d, m, bits, gs, qfn, sym, kind = _golden_cases()[case]
     got, meth = _run_case(g, name, d, m, bits, gs, qfn, sym)
     ref = g[f"{name}_Q"]
@@ -205,7 +212,7 @@ def test_gptq_groups_and_qfn_against_reference_golden(case):
 @pytest.mark.parametrize("gs,qfn,sym,bits", [(64, 'a', False, 3), (32, 'c', True, 4), (128, 'a', False, 2), (16, 'a', True, 4), (-1, 'c', False, 4)])
 def test_gptq_groups_kernel_equals_column_walk(gs, qfn, sym, bits):
     """same class, same inputs: the one-launch kernel against the reference-order column walk, both on the GPU in fp32"""
-    g = load_golden("gptq_groups")
+    g = _gptq_groups()
     outs = {}
     for use in (True, False):
         outs[use], meth = _run_case(g, "w3_g64_a", 384, 40, bits, gs, qfn, sym, use_kernel=use)
