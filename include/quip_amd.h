@@ -673,6 +673,26 @@ int quipamd_decode_attention(const void *q, const void *k, const void *v, void *
                              void *out, int dtype, int64_t bs, int heads, int hd, int64_t maxlen, float scale, int64_t ld,
                              void *stream);
 
+/* ---- grouped-query decode attention (Llama-2-70B class: heads / kv_heads = g query heads share one key / value head) ------------
+ * One decode step for bs sequences, one launch:
+ *   kcache/vcache[b, h, *pos, :] = k/v[b, h*hd : (h+1)*hd]   (k rotated first when tables are given);
+ *   out[b, j*hd + :] = softmax(scale q_j.K_h[0..*pos]^T) V_h[0..*pos],  h = j / g  (HF's repeat_kv order)
+ *   q: [bs, heads*hd] (row stride ldq), k / v: [bs, kv_heads*hd] (ldk, ldv), all strides multiples of 8 elements; out: [bs, heads*hd]
+ *   contiguous; kcache, vcache: [bs, kv_heads, maxlen, hd] contiguous; f16 / bf16; hd 64 or 128; 2 <= g <= 16; maxlen <= 32768;
+ *   pos: DEVICE int64 (hipGraph replay).  cos_table / sin_table: float [table_rows, hd] in HF's duplicated-halves layout, or both null:
+ *   q and this token's k are rotated exactly as quipamd_rope_inplace does (no rotation at a position past the tables).
+ *   Every cached K / V row is read once per (sequence, kv head); the cached positions are split over workgroups by 256 and merged in
+ *   a fixed order inside the launch (bit-identical runs).  fp32 scores, softmax and accumulation.  A position outside [0, maxlen)
+ *   makes the launch a no-op.
+ *   workspace: quipamd_decode_attention_grouped_workspace_bytes(...) bytes, 16-byte aligned and ZERO-FILLED before its first launch
+ *   (arrival counters the launch re-arms itself; partials); 0 bytes (null allowed) when maxlen <= 256.  One workspace may serve any
+ *   number of launches that run one after the other on a stream. */
+int64_t quipamd_decode_attention_grouped_workspace_bytes(int64_t bs, int heads, int kv_heads, int hd, int64_t maxlen);
+int quipamd_decode_attention_grouped(const void *q, const void *k, const void *v, void *kcache, void *vcache, const int64_t *pos,
+                                     void *out, const float *cos_table, const float *sin_table, int64_t table_rows, int dtype,
+                                     int64_t bs, int heads, int kv_heads, int hd, int64_t maxlen, float scale, int64_t ldq,
+                                     int64_t ldk, int64_t ldv, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

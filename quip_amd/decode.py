@@ -252,30 +252,37 @@ class RMSNorm(nn.Module):
 
 
 class LlamaBlock(nn.Module):
-    def __init__(self, n1, q_proj, k_proj, v_proj, o_proj, n2, gate_proj, up_proj, down_proj, heads):
+    def __init__(self, n1, q_proj, k_proj, v_proj, o_proj, n2, gate_proj, up_proj, down_proj, heads, kv_heads=None):
         super().__init__()
         self.n1, self.n2 = n1, n2
         self.q_proj, self.k_proj, self.v_proj, self.o_proj = q_proj, k_proj, v_proj, o_proj
         self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
         self.h = n1.weight.numel()
         self.heads, self.hd = heads, self.h // heads
+        self.kv_heads = kv_heads or heads          # < heads: grouped-query attention (k / v have kv_heads * hd outputs)
         self.fused = False
 
     @classmethod
-    def random(cls, h, ffn, heads, eps, dtype):
+    def random(cls, h, ffn, heads, eps, dtype, kv_heads=None):
         mk = lambda i, o: nn.Linear(i, o, bias=False, dtype=dtype)
-        return cls(RMSNorm(h, eps, dtype), mk(h, h), mk(h, h), mk(h, h), mk(h, h), RMSNorm(h, eps, dtype), mk(h, ffn), mk(h, ffn), mk(ffn, h), heads)
+        kv = (kv_heads or heads) * (h // heads)
+        return cls(RMSNorm(h, eps, dtype), mk(h, h), mk(h, kv), mk(h, kv), mk(h, h), RMSNorm(h, eps, dtype), mk(h, ffn), mk(h, ffn), mk(ffn, h), heads,
+                   kv_heads)
 
-    def forward(self, x, kc, vc, pos, cos, sin):
-        """x [bs, h]; kc / vc [bs, heads, maxlen, hd]; pos int64 [1] on the device; cos / sin fp32 [maxpos, hd]."""
+    def forward(self, x, kc, vc, pos, cos, sin, workspace=None):
+        """x [bs, h]; kc / vc [bs, kv_heads, maxlen, hd]; pos int64 [1] on the device; cos / sin fp32 [maxpos, hd];
+        workspace: ops.decode_attention_grouped_workspace for the caches' shape (grouped-query blocks)."""
         if self.fused:
             q, k, v = packed_forward_fused([self.q_proj, self.k_proj, self.v_proj], x, ln=self.n1)
         else:
             hn = self.n1(x)
             q, k, v = self.q_proj(hn), self.k_proj(hn), self.v_proj(hn)
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        ops.rope_inplace(q, k, cos, sin, pos, self.heads)
-        o = ops.decode_attention(q, k, v, kc, vc, pos)
+        if self.kv_heads < self.heads:                      # rotary + append + attention in one launch (csrc/decode_gqa.hip)
+            o = ops.decode_attention_grouped(q, k, v, kc, vc, pos, cos, sin, workspace=workspace)
+        else:
+            ops.rope_inplace(q, k, cos, sin, pos, self.heads)
+            o = ops.decode_attention(q, k, v, kc, vc, pos)
         if self.fused:
             x = packed_forward_fused([self.o_proj], o, residual=x)[0]
             g, u = packed_forward_fused([self.gate_proj, self.up_proj], x, ln=self.n2)
@@ -315,9 +322,15 @@ class LlamaDecoder(nn.Module):
     fused_head = False       # with v3: embedding (+ the previous step's argmax) and [U_down^T + residual -> final RMSNorm -> lm_head -> argmax
                              # partials, pos += 1] as one launch each (csrc/decode_head.hip)
 
+    attn_workspace = None    # grouped-query blocks: the engine's ops.decode_attention_grouped_workspace (set by DecodeEngine per step)
+
     @property
     def head_weight(self):
         return self.lm_head.weight
+
+    @property
+    def kv_heads(self):
+        return self.blocks[0].kv_heads if len(self.blocks) else self.heads
 
     def packed(self):
         return all(_is_packed(*(getattr(b, n) for n in self.NAMES)) for b in self.blocks)
@@ -389,7 +402,7 @@ class LlamaDecoder(nn.Module):
         if self.v3:
             return self.head(self.step_v3(x, pos, caches))
         for blk, (kc, vc) in zip(self.blocks, caches):
-            x = blk(x, kc, vc, pos, self.cos, self.sin)
+            x = blk(x, kc, vc, pos, self.cos, self.sin, self.attn_workspace)
         return self.head(x)
 
 
@@ -413,18 +426,22 @@ def decoder_from_hf(model, max_len=2048):
     if mt == "llama":
         m = model.model
         heads = cfg.num_attention_heads
-        if getattr(cfg, "num_key_value_heads", heads) != heads:
-            raise NotImplementedError("grouped-query attention is not served by the decode engine (Llama-2-7B/13B are multi-head)")
+        kv_heads = getattr(cfg, "num_key_value_heads", None) or heads
         if cfg.hidden_act != "silu" or getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False):
             raise NotImplementedError("Llama decode engine: SiLU gate, no biases")
         hd = getattr(cfg, "head_dim", None) or cfg.hidden_size // heads
         if hd * heads != cfg.hidden_size:
             raise NotImplementedError("head_dim * heads != hidden_size")
+        if kv_heads != heads:                           # grouped-query attention: csrc/decode_gqa.hip's shapes
+            g = heads // kv_heads
+            if heads % kv_heads or not 2 <= g <= 16 or hd not in (64, 128):
+                raise NotImplementedError(f"grouped-query attention with {heads} heads over {kv_heads} key / value heads of dim {hd} "
+                                          "(served: heads / kv_heads in 2..16, head_dim 64 or 128)")
         rot = m.rotary_emb
         if float(getattr(rot, "attention_scaling", 1.0)) != 1.0:
             raise NotImplementedError("scaled rotary embeddings")
         blocks = [LlamaBlock(l.input_layernorm, l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj, l.self_attn.o_proj,
-                             l.post_attention_layernorm, l.mlp.gate_proj, l.mlp.up_proj, l.mlp.down_proj, heads) for l in m.layers]
+                             l.post_attention_layernorm, l.mlp.gate_proj, l.mlp.up_proj, l.mlp.down_proj, heads, kv_heads) for l in m.layers]
         return LlamaDecoder(m.embed_tokens, blocks, m.norm, model.lm_head, heads, rot.inv_freq, max_len)
     raise NotImplementedError(f"decode engine: model_type {mt!r} (the reference drives OPT and Llama)")
 
@@ -451,7 +468,7 @@ def best_mode(dec, bs, dtype):
 
 
 class DecodeEngine:
-    """benchmark()'s per-token loop as ONE hipGraph replay per token: static KV cache [bs, heads, max_len, hd] per block, position and
+    """benchmark()'s per-token loop as ONE hipGraph replay per token: static KV cache [bs, kv_heads, max_len, hd] per block, position and
     current token on the device.  `forward(ids)` is `model(ids, past_key_values=...)` for the next position; `generate` is greedy."""
 
     def __init__(self, decoder, bs=1, max_len=2048, mode="auto", graph=True):
@@ -467,8 +484,12 @@ class DecodeEngine:
         self.mode = best_mode(decoder, bs, self.dtype) if mode == "auto" else mode
         set_mode(decoder, self.mode)
         hd = decoder.h // decoder.heads
-        z = lambda: torch.zeros(bs, decoder.heads, max_len, hd, dtype=self.dtype, device=self.dev)
+        kv_heads = decoder.kv_heads
+        z = lambda: torch.zeros(bs, kv_heads, max_len, hd, dtype=self.dtype, device=self.dev)
         self.caches = [(z(), z()) for _ in range(decoder.layers_n)]
+        # grouped-query attention: one workspace for every block's launch (they run one after another), allocated here, never per step
+        self.attn_workspace = (ops.decode_attention_grouped_workspace(bs, decoder.heads, kv_heads, hd, max_len, self.dev)
+                               if kv_heads < decoder.heads else None)
         self.arange = torch.arange(max_len, device=self.dev)
         self.ids = torch.zeros(bs, dtype=torch.int64, device=self.dev)
         self.pos = torch.zeros(1, dtype=torch.int64, device=self.dev)
@@ -497,6 +518,8 @@ class DecodeEngine:
 
     # -- one step ---------------------------------------------------------------------------------
     def _one(self):
+        if self.attn_workspace is not None:              # (a decoder may serve several engines: each step brings its own)
+            self.dec.attn_workspace = self.attn_workspace
         if self._fh:
             self.dec.step_fused_head(self.ids, self.pos, self.caches, self.logits, self.part_val, self.part_idx)
             return

@@ -1160,6 +1160,46 @@ def decode_attention(q, k, v, kcache, vcache, pos, scale=None):
     return out
 
 
+def decode_attention_grouped_workspace(bs, heads, kv_heads, hd, maxlen, device):
+    """the zero-filled workspace quipamd_decode_attention_grouped needs for this shape (arrival counters, which every launch re-arms, and
+    the partials of the split over positions); one workspace serves any number of launches that run one after another on a stream."""
+    n = int(_lib.load().quipamd_decode_attention_grouped_workspace_bytes(int(bs), int(heads), int(kv_heads), int(hd), int(maxlen)))
+    return torch.zeros(max(n, 16), dtype=torch.uint8, device=device)
+
+
+def decode_attention_grouped(q, k, v, kcache, vcache, pos, cos_table=None, sin_table=None, scale=None, workspace=None):
+    """one decode step of grouped-query attention, one launch (quip_amd/csrc/decode_gqa.hip): query head j reads key / value head
+    j // g, g = heads / kv_heads (HF's repeat_kv order), and every cached K / V row is read once per (sequence, kv head).
+    q: [bs, heads*hd]; k, v: [bs, kv_heads*hd] f16/bf16; kcache, vcache: [bs, kv_heads, maxlen, hd] contiguous (updated in place at *pos);
+    pos: int64 [1] ON THE DEVICE; cos_table / sin_table: float32 [rows, hd] (HF's duplicated-halves layout) to rotate q and this token's
+    k first, exactly as rope_inplace does; workspace: decode_attention_grouped_workspace(...) (allocated here when None -- give one
+    when the call is captured in a graph).  Returns out [bs, heads*hd]."""
+    _need_gpu(q, k, v, kcache, vcache, pos, cos_table, sin_table, workspace)
+    bs, kv_heads, maxlen, hd = kcache.shape
+    assert q.dim() == 2 and q.shape[0] == bs and q.shape[1] % hd == 0
+    heads = q.shape[1] // hd
+    assert k.shape == (bs, kv_heads * hd) and v.shape == k.shape
+    assert kcache.is_contiguous() and vcache.is_contiguous() and vcache.shape == kcache.shape
+    assert pos.dtype == torch.int64 and pos.numel() == 1
+    assert q.dtype == k.dtype == v.dtype == kcache.dtype == vcache.dtype
+    assert all(t.stride(-1) == 1 for t in (q, k, v))
+    ld = lambda t: t.stride(0) if bs > 1 else t.shape[1]
+    rows = 0
+    if cos_table is not None or sin_table is not None:
+        assert cos_table is not None and sin_table is not None and cos_table.dtype == sin_table.dtype == torch.float32
+        assert cos_table.shape == sin_table.shape and cos_table.shape[1] == hd and cos_table.is_contiguous() and sin_table.is_contiguous()
+        rows = cos_table.shape[0]
+    if workspace is None:
+        workspace = decode_attention_grouped_workspace(bs, heads, kv_heads, hd, maxlen, q.device)
+    assert workspace.is_contiguous()
+    out = torch.empty((bs, heads * hd), dtype=q.dtype, device=q.device)
+    sc = float(scale) if scale is not None else 1.0 / (hd ** 0.5)
+    _lib.call("quipamd_decode_attention_grouped", _p(q), _p(k), _p(v), _p(kcache), _p(vcache), _p(pos), _p(out), _p(cos_table), _p(sin_table),
+              rows, _dtype(q), bs, heads, kv_heads, hd, maxlen, ctypes.c_float(sc), ld(q), ld(k), ld(v), _p(workspace),
+              workspace.numel() * workspace.element_size(), _stream())
+    return out
+
+
 def decode_attention_fused(Uops, ys, biases, kcache, vcache, pos, cos_table=None, sin_table=None, scale=None):
     """decode attention with the output-side operators of q / k / v in its prologue (quipamd_decode_attention_fused):
     Uops: the three OrthoOp of the projections (applied transposed); ys: their GEMM outputs in the projected basis, fp16 [bs, heads*hd];

@@ -527,6 +527,17 @@ def packed_forward_fused(qls, x, ln=None, residual=None, relu=False, gate_up=Non
         if not (in_kernel or in_blk):
             x, gate_up = torch.nn.functional.silu(x) * gate_up, None
     same = len({(q.infeatures, q.outfeatures, q.bits) for q in qls}) == 1
+    if not same and gate_up is None and all(q.U is not None and q.V is not None and q.qfn == 'b' for q in qls) and rows <= ops.OrthoOp.SMALL_ROWS:
+        # layers of different shapes on one input (grouped-query attention: q [h] beside k, v [kv_heads * hd]): each equal-shape
+        # subgroup takes the three-launch form on its own
+        groups = {}
+        for i, q in enumerate(qls):
+            groups.setdefault((q.infeatures, q.outfeatures, q.bits), []).append(i)
+        outs = [None] * len(qls)
+        for idx in groups.values():
+            for i, o in zip(idx, packed_forward_fused([qls[i] for i in idx], x, ln=ln, residual=residual, relu=relu)):
+                outs[i] = o
+        return outs
     if not same or any(q.U is None or q.V is None or q.qfn != 'b' for q in qls) or rows > ops.OrthoOp.SMALL_ROWS:
         h = _norm(ln, x)
         outs = [q(h) for q in qls]

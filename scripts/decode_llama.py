@@ -14,7 +14,9 @@ Per block, fused variant:
 The 4096-wide operators (64 x 64) run on the tiled small-batch kernels (csrc/ortho_tile.hip); the 11008-wide ones do not fit a
 workgroup's LDS and take quipamd_ortho_apply_rows.
 
-usage: python scripts/decode_llama.py [--layers 32] [--tokens 64] [--prompt 64] [--check]"""
+usage: python scripts/decode_llama.py [--layers 32] [--tokens 64] [--prompt 64] [--check]
+       python scripts/decode_llama.py --h 8192 --ffn 28672 --heads 64 --kv-heads 8 --layers 4 --no-dense   # Llama-2-70B geometry, 4 blocks
+(kv heads < heads: grouped-query attention, csrc/decode_gqa.hip)"""
 import argparse
 import json
 import math
@@ -40,10 +42,12 @@ RMSNorm = decode.RMSNorm
 class Decoder(decode.LlamaDecoder):
     """quip_amd.decode.LlamaDecoder (plain / fused / v3 / fused-head steps live in the package) over random-init modules"""
 
-    def __init__(self, layers=32, h=4096, ffn=11008, heads=32, vocab=32000, maxpos=4096, eps=1e-5, theta=10000.0, dtype=torch.float16):
+    def __init__(self, layers=32, h=4096, ffn=11008, heads=32, vocab=32000, maxpos=4096, eps=1e-5, theta=10000.0, dtype=torch.float16,
+                 kv_heads=None):
         hd = h // heads
         inv = 1.0 / (theta ** (torch.arange(0, hd, 2, dtype=torch.float32) / hd))          # LlamaRotaryEmbedding
-        super().__init__(nn.Embedding(vocab, h, dtype=dtype), [decode.LlamaBlock.random(h, ffn, heads, eps, dtype) for _ in range(layers)],
+        blocks = [decode.LlamaBlock.random(h, ffn, heads, eps, dtype, kv_heads=kv_heads) for _ in range(layers)]   # kv_heads < heads: GQA
+        super().__init__(nn.Embedding(vocab, h, dtype=dtype), blocks,
                          RMSNorm(h, eps, dtype), nn.Linear(h, vocab, bias=False, dtype=dtype), heads, inv, maxpos)
 
 
@@ -74,9 +78,9 @@ def pack_model(model, bits, dev, seed=0, twin=True):
     return dense, nbytes
 
 
-def build(layers, dev, dtype, small=False):
+def build(layers, dev, dtype, small=False, **geom):
     torch.manual_seed(0)
-    kw = dict(h=2048, ffn=11008, heads=16) if small else {}     # small: 64 x 32 operators; 11008 keeps the 688 x 16 general path
+    kw = dict(h=2048, ffn=11008, heads=16) if small else geom     # small: 64 x 32 operators; 11008 keeps the 688 x 16 general path
     model = Decoder(layers=layers, dtype=dtype, **kw).to(dev).eval()
     for p_ in model.parameters():
         if p_.dim() > 1:
@@ -84,13 +88,15 @@ def build(layers, dev, dtype, small=False):
     return model
 
 
-def run(layers=32, bits=2, bs=1, prompt=64, tokens=64, with_dense=True):
+def run(layers=32, bits=2, bs=1, prompt=64, tokens=64, with_dense=True, h=4096, ffn=11008, heads=32, kv_heads=None, vocab=32000):
     dev, dtype = torch.device("cuda:0"), torch.float16
     maxlen = prompt + tokens + 8
-    model = build(layers, dev, dtype)
-    out = {"config": {"arch": "Llama-2-7B (hidden 4096, intermediate 11008, heads 32 x 128, vocab 32000)", "layers": layers, "bits": bits,
-                      "bs": bs, "prompt": prompt, "tokens": tokens, "launch": "hipGraph",
-                      "weights": "random init, nearest-rounded qfn-b codes, Kronecker U/V (64x64, 688x16), random scaleWH"}}
+    kv_heads = kv_heads or heads
+    model = build(layers, dev, dtype, h=h, ffn=ffn, heads=heads, kv_heads=kv_heads, vocab=vocab, maxpos=max(4096, maxlen))
+    arch = "Llama-2-7B" if (h, ffn, heads, kv_heads) == (4096, 11008, 32, 32) else "Llama-2-70B" if (h, ffn, heads, kv_heads) == (8192, 28672, 64, 8) else "Llama"
+    out = {"config": {"arch": f"{arch} (hidden {h}, intermediate {ffn}, heads {heads} x {h // heads}, kv heads {kv_heads}, vocab {vocab})",
+                      "layers": layers, "bits": bits, "bs": bs, "prompt": prompt, "tokens": tokens, "launch": "hipGraph",
+                      "weights": "random init, nearest-rounded qfn-b codes, Kronecker U/V, random scaleWH"}}
     if with_dense:
         med, _, _ = D.time_decode(model, bs, prompt, tokens, maxlen, dev, dtype, False)
         out["dense_fp16"] = {"ms_per_token_median": med * 1e3, "tok_per_s": bs / med,
@@ -98,12 +104,15 @@ def run(layers=32, bits=2, bs=1, prompt=64, tokens=64, with_dense=True):
     _, nbytes = pack_model(model, bits, dev, twin=False)
     med, _, _ = D.time_decode(model, bs, prompt, tokens, maxlen, dev, dtype, False)
     head = model.lm_head.weight.numel() * 2
-    out["packed_w%d" % bits] = {"ms_per_token_median": med * 1e3, "tok_per_s": bs / med, "packed_weight_MB": nbytes / 1e6,
+    # K / V bytes one step reads at the timed positions' mean depth (prompt + tokens / 2), every block
+    kv_bytes = layers * 2 * bs * kv_heads * (prompt + tokens / 2) * (h // heads) * 2
+    out["packed_w%d" % bits] = {"ms_per_token_median": med * 1e3, "tok_per_s": bs / med, "packed_weight_MB": nbytes / 1e6, "kv_MB_per_step": kv_bytes / 1e6,
                                 "hbm_bound_tok_per_s": 8e12 / (nbytes + head), "what": "QuantLinear.forward per layer (3 launches each), torch RMSNorm / silu"}
+    bound_s = (nbytes + head + kv_bytes) / 8e12
     for blk in model.blocks:
         blk.fused = True
     med, _, _ = D.time_decode(model, bs, prompt, tokens, maxlen, dev, dtype, False)
-    out["packed_w%d_fused" % bits] = {"ms_per_token_median": med * 1e3, "tok_per_s": bs / med,
+    out["packed_w%d_fused" % bits] = {"ms_per_token_median": med * 1e3, "tok_per_s": bs / med, "frac_of_byte_bound": bound_s / med,
                                       "what": "q/k/v and gate/up grouped; RMSNorm folded into the V-side launch; residual folded into U^T; "
                                               "4096-wide operators tiled over 16 workgroups"}
     if model.v3_ok(bs):
@@ -164,5 +173,11 @@ if __name__ == "__main__":
         ap.add_argument("--prompt", type=int, default=64)
         ap.add_argument("--tokens", type=int, default=64)
         ap.add_argument("--no-dense", action="store_true")
+        ap.add_argument("--h", type=int, default=4096)
+        ap.add_argument("--ffn", type=int, default=11008)
+        ap.add_argument("--heads", type=int, default=32)
+        ap.add_argument("--kv-heads", type=int, default=None, help="key / value heads (default: --heads; Llama-2-70B: 8)")
+        ap.add_argument("--vocab", type=int, default=32000)
         a = ap.parse_args()
-        print(json.dumps(run(a.layers, a.bits, a.bs, a.prompt, a.tokens, with_dense=not a.no_dense)))
+        print(json.dumps(run(a.layers, a.bits, a.bs, a.prompt, a.tokens, with_dense=not a.no_dense, h=a.h, ffn=a.ffn, heads=a.heads,
+                             kv_heads=a.kv_heads, vocab=a.vocab)))

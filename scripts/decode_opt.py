@@ -152,8 +152,11 @@ FAST_ARGMAX = True
 
 def time_decode(model, bs, prompt, tokens, maxlen, dev, dtype, eager):
     heads, hd = model.heads, model.h // model.heads
-    caches = [(torch.zeros(bs, heads, maxlen, hd, dtype=dtype, device=dev), torch.zeros(bs, heads, maxlen, hd, dtype=dtype, device=dev))
+    kv = getattr(model, "kv_heads", heads)                  # grouped-query Llama: the caches hold the key / value heads only
+    caches = [(torch.zeros(bs, kv, maxlen, hd, dtype=dtype, device=dev), torch.zeros(bs, kv, maxlen, hd, dtype=dtype, device=dev))
               for _ in range(model.layers_n)]
+    if kv < heads:
+        model.attn_workspace = ops.decode_attention_grouped_workspace(bs, heads, kv, hd, maxlen, dev)
     arange = torch.arange(maxlen, device=dev)
     ids = torch.randint(0, min(50000, model.tok.weight.shape[0]), (bs,), device=dev)
     pos = torch.zeros(1, dtype=torch.int64, device=dev)
