@@ -415,6 +415,12 @@ int quipamd_decode_attention_fused(const quipamd_fop *U, const void *const *y, c
  * passes; 0 = never, negative = the default.  `one_group_from`: a 4-wave form whose one wave group runs the three passes in turn (two
  * workgroups per CU); measured slower (csrc/decode_attn.hip), default 0 = never.  All forms compute the same values in the same order. */
 void quipamd_decode_attention_config(int one_group_from, int three_heads_from);
+/* The largest maxlen any form of quipamd_decode_attention_fused serves for head_dim hd with a p x q operator, 0 for a shape it does not
+ * serve.  Host arithmetic only.  A workgroup holds the three operator images and fp32 scores of maxlen positions per wave group in at most
+ * 160 KiB of LDS: the three-heads form holds three groups' scores and serves up to 3972 / 8548 / 8196 positions (head_dim 128 with 64 x 64,
+ * 64 with 64 x 32, 128 with 64 x 32); past that the launch takes the one-head form, which serves up to 13360 / 26384 / 26032 (this value).
+ * quipamd_decode_attention_fused refuses a longer cache with QUIPAMD_ERR_SHAPE before any device call. */
+int64_t quipamd_decode_attention_fused_max_len(int hd, int p, int q);
 
 /* The output side of a packed layer on its own (the end of the last decoder block): out = [relu](U^T y + bias + residual), fp16.
  * U: the TRANSPOSED operator (quipamd_fop; 64 x 32, 64 x 64 or 128 x 64); y: fp16 [bs, n] in ZT order (see below); bias fp16 [n];

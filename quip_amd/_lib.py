@@ -72,6 +72,7 @@ SIGNATURES = {
     "quipamd_decode_u_only": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_vp],
     "quipamd_argmax_rows": [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp],
     "quipamd_decode_attention_fused": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_i64, c_float, c_i64, c_vp],
+    "quipamd_decode_attention_fused_max_len": [c_int, c_int, c_int],
     "quipamd_rope_inplace": [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_vp],
     "quipamd_cholesky_lt": [c_vp, c_vp, c_i64, c_vp, c_vp],
     "quipamd_preproc_workspace_bytes": [c_i64, c_i64],
@@ -120,7 +121,7 @@ def load():
         fn.restype = (ctypes.c_char_p if name == "quipamd_last_error" else None if name in ("quipamd_vecquant_invalidate", "quipamd_cholesky_config", "quipamd_ldlq_config", "quipamd_gptq_qfnb_debug", "quipamd_ortho_blocked_config",
                                                                                                       "quipamd_dequant_gemm_grouped_config", "quipamd_decode_attention_config") else
                       c_i64 if name in ("quipamd_hessian_fast_workspace", "quipamd_vecquant_workspace_bytes", "quipamd_gptq_qfnb_workspace_bytes", "quipamd_gptq_qfnb_info_offset", "quipamd_preproc_workspace_bytes",
-                                                          "quipamd_decode_attention_grouped_workspace_bytes") else c_int)
+                                                          "quipamd_decode_attention_grouped_workspace_bytes", "quipamd_decode_attention_fused_max_len") else c_int)
     _lib = lib
     return lib
 

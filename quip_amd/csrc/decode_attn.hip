@@ -267,6 +267,12 @@ struct AttnUArgs {
     QaPfList pf;                          // operands of a later launch, touched by QA_PF_WGS extra workgroups (csrc/prefetch.h); n = 0: none
 };
 
+// LDS of one wave group's attention buffers: q / k / v slices (f16 3 x HD) + 32, scores [maxlen], red [8], part [4 x HD], 16-byte rounded
+__host__ __device__ inline size_t attn_u_group_bytes(int hd, int64_t maxlen)
+{
+    return (3 * (size_t)hd * 2 + 32 + (size_t)(maxlen + 8 + 4 * (int64_t)hd) * sizeof(float) + 15) & ~(size_t)15;
+}
+
 // 768 threads: waves 0-3 / 4-7 / 8-11 run the operator pass of q / k / v side by side (round 3a ran the three passes one after the other on
 // four waves: two passes' worth of copy, stage 1 and stage 2 on the launch's critical path); waves 4-11 leave after their pass, the first
 // 256 threads go on to the gather, the rotary embedding and the attention itself.
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(256 * NGRP) void decode_attn_u_kernel(AttnUArgs G)
     // [3 image sets][q k v slices f16 3 x HD][scores maxlen][red 8][part 4 x HD]
     char *img = smem_u;
     static_assert(!MH || NGRP == 3, "three heads per workgroup ride on the three wave groups");
-    const size_t AB = (3 * HD * 2 + 32 + (size_t)(G.maxlen + 8 + 4 * HD) * sizeof(float) + 15) & ~(size_t)15;     // one group's attention buffers
+    const size_t AB = attn_u_group_bytes(HD, G.maxlen);                                                            // one group's attention buffers
     char *abuf = smem_u + 3 * D::BYTES + (MH ? (size_t)(threadIdx.x >> 8) * AB : 0);
     uint16_t *qkv = reinterpret_cast<uint16_t *>(abuf);
     float *scores = reinterpret_cast<float *>(abuf + 3 * HD * 2 + 32);
@@ -560,17 +566,35 @@ __global__ __launch_bounds__(256 * NGRP) void decode_attn_u_kernel(AttnUArgs G)
     QA_LOG(1)
 }
 
+// LDS of a workgroup of the fused launch: the three operator images and the attention buffers of one wave group, of three with three heads per
+// workgroup (the 4-wave form holds what the one-head 12-wave form holds).  The launch, the choice of form and the maxlen query all read it here.
+constexpr size_t ATTN_U_LDS_MAX = 160 * 1024;
+template <int HD, int P, int Q> size_t attn_u_lds(int64_t maxlen, bool three_heads)
+{
+    return 3 * PassDims<P, Q, 4>::BYTES + (three_heads ? 3 : 1) * attn_u_group_bytes(HD, maxlen);
+}
+
+// the largest maxlen (at most the entry point's 32768) whose LDS fits a workgroup of the form
+template <int HD, int P, int Q> int64_t attn_u_max_len(bool three_heads)
+{
+    int64_t lo = 0, hi = 32768;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (attn_u_lds<HD, P, Q>(mid, three_heads) <= ATTN_U_LDS_MAX) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
 template <int HD, int P, int Q, int NGRP, bool MH = false> int launch_attn_u_n(const AttnUArgs &A, int64_t bs, hipStream_t s)
 {
-    typedef PassDims<P, Q, 4> D;
-    const size_t ab = (3 * HD * 2 + 32 + (size_t)(A.maxlen + 8 + 4 * HD) * sizeof(float) + 15) & ~(size_t)15;     // one group's attention buffers
-    const size_t lds = 3 * D::BYTES + (MH ? 3 : 1) * ab;
+    const size_t lds = attn_u_lds<HD, P, Q>(A.maxlen, MH);
     auto kern = decode_attn_u_kernel<HD, P, Q, NGRP, MH>;
     static size_t reserved[64] = {};
     int dev = 0;
     (void)hipGetDevice(&dev);
     const bool known = dev >= 0 && dev < 64;
-    if (lds > 160 * 1024) return qa_fail(QUIPAMD_ERR_SHAPE, "decode_attention_fused: %zu B of LDS (maxlen too large for this operator shape)", lds);
+    if (lds > ATTN_U_LDS_MAX) return qa_fail(QUIPAMD_ERR_SHAPE, "decode_attention_fused: %zu B of LDS (maxlen too large for this operator shape)", lds);
     if (lds > 48 * 1024 && (!known || lds > reserved[dev])) {
         if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_attention_fused: cannot reserve %zu B of LDS", lds);
@@ -591,13 +615,15 @@ template <int HD, int P, int Q, int NGRP, bool MH = false> int launch_attn_u_n(c
 //     1.41-1.42 -> 1.45 ms per step, Llama-2-7B 2.98 -> 3.07 (profiles/r06D_attn_forms.jsonl): what the second round cost, the serial passes and
 //     two workgroups on one CU's memory path cost again.  Forced only (one_group_from).
 //   * three heads per workgroup (MH above): a third of the workgroups and of the redundant operator passes; default from more than one
-//     (sequence, head) pair per CU on.
+//     (sequence, head) pair per CU on -- where its three groups' scores fit the LDS: past that (maxlen 3972 at head dim 128 with a 64 x 64
+//     operator) the one-head form serves the cache, forced or not.
 int g_attn_u_one_group_from = 0;       // (sequence, head) pairs from which the 4-wave form is launched (0 = never)
 int g_attn_u_three_heads_from = 257;   // ... from which a workgroup serves three heads (0 = never)
 template <int HD, int P, int Q> int launch_attn_u(const AttnUArgs &A, int64_t bs, hipStream_t s)
 {
     if (g_attn_u_one_group_from > 0 && bs * A.heads >= g_attn_u_one_group_from) return launch_attn_u_n<HD, P, Q, 1>(A, bs, s);
-    if (g_attn_u_three_heads_from > 0 && bs * A.heads >= g_attn_u_three_heads_from) return launch_attn_u_n<HD, P, Q, 3, true>(A, bs, s);
+    if (g_attn_u_three_heads_from > 0 && bs * A.heads >= g_attn_u_three_heads_from && attn_u_lds<HD, P, Q>(A.maxlen, true) <= ATTN_U_LDS_MAX)
+        return launch_attn_u_n<HD, P, Q, 3, true>(A, bs, s);
     return launch_attn_u_n<HD, P, Q, 3>(A, bs, s);
 }
 
@@ -794,6 +820,14 @@ extern "C" void quipamd_decode_attention_config(int one_group_from, int three_he
     g_attn_u_three_heads_from = three_heads_from < 0 ? 257 : three_heads_from;       // (negative: the default)
 }
 
+extern "C" int64_t quipamd_decode_attention_fused_max_len(int hd, int p, int q)
+{
+    if (hd == 64 && p == 64 && q == 32) return attn_u_max_len<64, 64, 32>(false);
+    if (hd == 128 && p == 64 && q == 64) return attn_u_max_len<128, 64, 64>(false);
+    if (hd == 128 && p == 64 && q == 32) return attn_u_max_len<128, 64, 32>(false);
+    return 0;
+}
+
 extern "C" int quipamd_decode_attention_fused(const quipamd_fop *U, const void *const *y, const void *const *bias, void *kcache, void *vcache,
                                               const int64_t *pos, void *out, const float *cos_table, const float *sin_table,
                                               int64_t table_rows, int64_t bs, int heads, int hd, int64_t maxlen, float scale, int64_t ldo,
@@ -814,6 +848,9 @@ extern "C" int quipamd_decode_attention_fused(const quipamd_fop *U, const void *
     }
     A.kc = (uint16_t *)kcache; A.vc = (uint16_t *)vcache; A.out = (uint16_t *)out; A.pos = pos; A.cos_t = cos_table; A.sin_t = sin_table;
     A.table_rows = table_rows; A.maxlen = maxlen; A.ldo = ldo; A.heads = heads; A.scale = scale;
+    const int64_t cap = quipamd_decode_attention_fused_max_len(hd, p, q);          // (0: a shape no instantiation serves, refused below)
+    QA_REQUIRE(cap == 0 || maxlen <= cap, QUIPAMD_ERR_SHAPE, "decode_attention_fused: maxlen %lld > %lld, the most any form holds in %zu B of LDS "
+               "(head_dim %d, %d x %d operator)", (long long)maxlen, (long long)cap, ATTN_U_LDS_MAX, hd, p, q);
     hipStream_t s = (hipStream_t)stream;
     if (hd == 64 && p == 64 && q == 32) return launch_attn_u<64, 64, 32>(A, bs, s);
     if (hd == 128 && p == 64 && q == 64) return launch_attn_u<128, 64, 64>(A, bs, s);

@@ -152,7 +152,8 @@ class OPTDecoder(nn.Module):
     def packed(self):
         return all(_is_packed(b.q_proj, b.k_proj, b.v_proj, b.out_proj, b.fc1, b.fc2) for b in self.blocks)
 
-    def v3_ok(self, bs):
+    def v3_ok(self, bs, max_len=None):
+        """(max_len: no bound here -- a block whose cache the fused attention launch cannot hold runs ops.decode_attention, blocks_v3)"""
         b = self.blocks[0]
         return (self.packed() and fused_ok([b.q_proj, b.k_proj, b.v_proj], bs, prev=b.fc2) and fused_ok([b.out_proj], bs, norm=False)
                 and fused_ok([b.fc1], bs, prev=b.out_proj) and fused_ok([b.fc2], bs, prev=b.fc1, norm=False, residual=False))
@@ -335,13 +336,16 @@ class LlamaDecoder(nn.Module):
     def packed(self):
         return all(_is_packed(*(getattr(b, n) for n in self.NAMES)) for b in self.blocks)
 
-    def v3_ok(self, bs):
+    def v3_ok(self, bs, max_len=None):
+        """can mode v3 run `bs` sequences over KV caches of max_len positions (default: the rotary tables' rows)?  blocks_v3 has no other
+        attention than the fused launch, whose LDS bounds the cache (ops.decode_attention_fused_max_len)."""
         b = self.blocks[0]
         qkv = [b.q_proj, b.k_proj, b.v_proj]
+        max_len = self.cos.shape[0] if max_len is None else max_len
         return (self.packed() and fused_ok(qkv, bs, prev=b.down_proj) and fused_ok([b.o_proj], bs, norm=False)
                 and fused_ok([b.gate_proj, b.up_proj], bs, prev=b.o_proj) and b.down_proj.U is not None and b.down_proj.U.fused_ok
                 and bigp_tail_ok([b.gate_proj, b.up_proj], b.down_proj, bs)
-                and fused_attention_ok(qkv, torch.empty((bs, self.heads, 1, b.hd), dtype=torch.float16, device='meta')))
+                and fused_attention_ok(qkv, torch.empty((bs, self.heads, max_len, b.hd), dtype=torch.float16, device='meta')))
 
     def head_ok(self, bs):
         return fused_head_ok(self.blocks[-1].down_proj, bs, self.norm)
@@ -458,10 +462,10 @@ def set_mode(dec, mode):
     dec.mode = mode
 
 
-def best_mode(dec, bs, dtype):
-    """the fastest launch sequence the decoder's layers allow (module docstring)"""
+def best_mode(dec, bs, dtype, max_len=None):
+    """the fastest launch sequence the decoder's layers allow (module docstring) for `bs` sequences over caches of max_len positions"""
     if dec.packed():
-        if dtype == torch.float16 and dec.v3_ok(bs):
+        if dtype == torch.float16 and dec.v3_ok(bs, max_len):
             return "v3_head" if dec.head_ok(bs) else "v3"
         return "fused"
     return "plain"
@@ -481,7 +485,7 @@ class DecodeEngine:
         elif getattr(decoder, "arch", None) == "llama":
             max_len = min(max_len, decoder.cos.shape[0])
         self.dev, self.dtype, self.bs, self.max_len = w.device, w.dtype, bs, max_len
-        self.mode = best_mode(decoder, bs, self.dtype) if mode == "auto" else mode
+        self.mode = best_mode(decoder, bs, self.dtype, max_len) if mode == "auto" else mode
         set_mode(decoder, self.mode)
         hd = decoder.h // decoder.heads
         kv_heads = decoder.kv_heads

@@ -5,6 +5,7 @@ gfx950 kernel from libquip_amd.so.  Inputs must live on a GPU -- there is no CPU
 raises), and a missing library raises at first use (quip_amd/_lib.py).
 """
 import ctypes
+import functools
 
 import torch
 
@@ -1198,6 +1199,13 @@ def decode_attention_grouped(q, k, v, kcache, vcache, pos, cos_table=None, sin_t
               rows, _dtype(q), bs, heads, kv_heads, hd, maxlen, ctypes.c_float(sc), ld(q), ld(k), ld(v), _p(workspace),
               workspace.numel() * workspace.element_size(), _stream())
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def decode_attention_fused_max_len(hd, p, q):
+    """the largest KV-cache maxlen decode_attention_fused serves for head_dim hd with p x q operators (its LDS limit), 0 for a shape it does
+    not serve (quipamd_decode_attention_fused_max_len)"""
+    return int(_lib.load().quipamd_decode_attention_fused_max_len(int(hd), int(p), int(q)))
 
 
 def decode_attention_fused(Uops, ys, biases, kcache, vcache, pos, cos_table=None, sin_table=None, scale=None):

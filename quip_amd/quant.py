@@ -818,11 +818,13 @@ def fused_head(ql, y, residual, ln, W, logits, part_val=None, part_idx=None, pos
 
 
 def fused_attention_ok(qkv, kcache):
+    """can `fused_attention` serve packed q / k / v layers `qkv` over this KV cache [bs, heads, maxlen, hd]?  (operator shape, fp16, and a
+    maxlen the launch's LDS holds: ops.decode_attention_fused_max_len)"""
     bs, heads, maxlen, hd = kcache.shape
     shapes = {(q.U.p, q.U.q) for q in qkv if q.U is not None}
     return (len(qkv) == 3 and all(q.U is not None and q.U.fused_ok for q in qkv) and len(shapes) == 1 and kcache.dtype == torch.float16
             and next(iter(shapes)) in (((64, 32),) if hd == 64 else ((64, 64), (64, 32)) if hd == 128 else ())
-            and all(q.outfeatures == heads * hd for q in qkv))
+            and all(q.outfeatures == heads * hd for q in qkv) and maxlen <= ops.decode_attention_fused_max_len(hd, *next(iter(shapes))))
 
 
 def fused_stage(qls, x=None, prev=None, y_prev=None, residual=None, relu=False, ln=None, store=False, y_dtype=torch.float32):

@@ -147,9 +147,9 @@ def harness_logits(dec, toks, maxlen, dtype, graph=True):
     return torch.stack(logits)
 
 
-def _gate(name, got, ref, toks):
+def _gate(name, got, ref, toks, tol=1e-2):
     rel = ((got - ref).norm(dim=1) / ref.norm(dim=1)).max().item()
-    assert rel <= 1e-2, (name, rel)
+    assert rel <= tol, (name, rel)
     top2 = ref.topk(2, dim=1).values
     margin = top2[:, 0] - top2[:, 1]
     diff = (got - ref).abs().max(dim=1).values
@@ -305,3 +305,131 @@ def test_llama_engine_many_sequences_matches_hf(bs):
     got = torch.stack(got)
     worst = max(_gate(f"llama-bs{bs}-seq{s}", got[:, s], seqs[s][1], seqs[s][0])[0] for s in range(bs))
     print(f"llama engine, {bs} sequences per step vs HF: worst max-rel logits err {worst:.2e}")
+
+
+# ---------------------------------------------------------------------------------- Llama-2-7B width at its context length
+_L7 = {}
+# Mode `fused` at this width is further from HF than the suite's 1e-2 at the last of 16 steps (measured 1.1e-2, max_len 4096 and 16384
+# alike; v3 5.3e-3, QuantLinear.forward per layer 4.0e-3): its K3 launches hand x~ over in bf16, 1.7-1.9e-3 per layer against the dense
+# twin where QuantLinear.forward is 4-9e-4, and 14 such layers compound.  A property of that mode's launches, not of the cache length.
+FUSED_7B_GATE = 1.5e-2
+
+
+def _llama7b(maxpos):
+    """2 layers of Llama-2-7B's width (hidden 4096: 64 x 64 operators, 32 heads of 128, intermediate 11008) with `maxpos` positions:
+    the packed decoder and the HF model holding its dense twins, built once per maxpos"""
+    from quip_amd import decode
+    if maxpos not in _L7:
+        L = _load("decode_llama")
+        dtype, eps = torch.float16, 1e-5
+        torch.manual_seed(0)
+        dec = L.Decoder(layers=2, h=4096, ffn=11008, heads=32, vocab=512, maxpos=maxpos, eps=eps, dtype=dtype).to(DEV).eval()
+        for p_ in dec.parameters():
+            if p_.dim() > 1:
+                p_.data.normal_(0, 0.02)
+            else:
+                p_.data.add_(0.05 * torch.randn_like(p_))
+        twin, _ = L.pack_model(dec, 2, DEV)
+        hf = hf_llama_from_decoder(dec, twin, 32, maxpos, eps, dtype, DEV)
+        # .to(float16) rounded HF's rotary frequencies to fp16 (up to 4e-4 off): harmless over 64 positions, ~1 rad at position 4080.
+        # Give HF the decoder's fp32 frequencies (decode_llama.Decoder's formula, checked against its tables).
+        inv = 1.0 / (10000.0 ** (torch.arange(0, 128, 2, dtype=torch.float32) / 128))
+        assert torch.equal(decode.rotary_tables(inv, maxpos)[0], dec.cos.cpu())
+        rot = hf.model.rotary_emb
+        rot.inv_freq = inv.to(DEV)
+        rot.original_inv_freq = inv.to(DEV)
+        _L7[maxpos] = (dec, hf)
+    return _L7[maxpos]
+
+
+def _engine_logits(eng, seqs):
+    """teacher-force every sequence's tokens through the engine: logits [steps, bs, vocab]"""
+    got = []
+    for i in range(len(seqs[0][0])):
+        ids = torch.tensor([s[0][i] for s in seqs], device=DEV)
+        got.append(eng.forward(ids).float().clone())
+    return torch.stack(got)
+
+
+def _engine_vs_hf(eng, seqs, name, tol=1e-2):
+    """gate each sequence's engine logits against HF's"""
+    got = _engine_logits(eng, seqs)
+    return max(_gate(f"{name}-seq{s}", got[:, s], seqs[s][1], seqs[s][0], tol)[0] for s in range(len(seqs)))
+
+
+@pytest.mark.parametrize("bs", [1, 9, 16])
+def test_llama_7b_width_engine_at_its_4096_context_matches_hf(bs):
+    """max_len 4096 in whatever mode best_mode picks (v3 / v3_head): from 9 sequences on, 288+ (sequence, head) pairs ask the fused attention
+    launch for its three-heads form, whose LDS does not fit a 4096-position cache -- it used to refuse the step"""
+    from quip_amd import decode
+    dec, hf = _llama7b(4096)
+    seqs = [hf_generate(hf, 7 + 31 * s, NTOK) for s in range(bs)]
+    eng = decode.DecodeEngine(dec, bs=bs, max_len=4096)
+    assert eng.mode in ("v3", "v3_head"), eng.mode
+    worst = _engine_vs_hf(eng, seqs, f"llama7b-bs{bs}")
+    print(f"llama 7b width, {bs} sequences, max_len 4096, mode {eng.mode} vs HF: worst max-rel logits err {worst:.2e} (gate 1e-2)")
+
+
+def _continue_at(eng, kvs, start):
+    """let the engine go on at position `start` over a prefix another implementation computed: kvs[layer] = (K, V) [bs, kv_heads, start, hd]
+    (post-rotary, like the engine's caches).  _prepare() -- warm-up and graph capture -- writes cache position 0 and resets the position,
+    so it runs first; then the prefix goes into the caches, and the device position and the step count step() checks against max_len
+    move to `start`."""
+    eng._prepare()
+    for (kc, vc), (K, V) in zip(eng.caches, kvs):
+        kc[:, :, :start].copy_(K)
+        vc[:, :, :start].copy_(V)
+    eng.pos.fill_(start)
+    eng._steps = start
+
+
+@torch.no_grad()
+def test_llama_7b_width_engine_near_the_end_of_its_context_matches_hf():
+    """9 sequences: HF prefills 4080 tokens of each (one call per sequence), its keys and values become the engine's caches, then 16 steps
+    up to position 4095 against HF fed past_key_values"""
+    from quip_amd import decode
+    dec, hf = _llama7b(4096)
+    bs, start, maxlen = 9, 4080, 4096
+    g = torch.Generator().manual_seed(4080)
+    prompts = torch.randint(0, dec.tok.weight.shape[0], (bs, start + 1), generator=g).to(DEV)
+    eng = decode.DecodeEngine(dec, bs=bs, max_len=maxlen)
+    assert eng.mode in ("v3", "v3_head"), eng.mode
+    kvs = [(torch.empty(bs, 32, start, 128, dtype=torch.float16, device=DEV), torch.empty(bs, 32, start, 128, dtype=torch.float16, device=DEV))
+           for _ in dec.blocks]
+    seqs = []
+    for s in range(bs):
+        pkv = hf(input_ids=prompts[s:s + 1, :start], use_cache=True).past_key_values
+        for li, (K, V) in enumerate(kvs):
+            K[s].copy_(pkv.layers[li].keys[0])
+            V[s].copy_(pkv.layers[li].values[0])
+        ids, toks, logits = prompts[s:s + 1, start:], [], []
+        for _ in range(maxlen - start):                                  # hf_generate's loop, from the prefilled cache
+            out = hf(input_ids=ids, past_key_values=pkv, use_cache=True)
+            pkv = out.past_key_values
+            lg = out.logits[0, -1].float()
+            toks.append(int(ids[0, 0]))
+            logits.append(lg.clone())
+            ids = lg.argmax().reshape(1, 1)
+        seqs.append((toks, torch.stack(logits)))
+        del pkv
+    _continue_at(eng, kvs, start)
+    worst = _engine_vs_hf(eng, seqs, "llama7b-end")
+    assert eng._steps == maxlen
+    print(f"llama 7b width, {bs} sequences, positions {start}..{maxlen - 1}, mode {eng.mode} vs HF: worst max-rel logits err {worst:.2e}")
+
+
+def test_llama_7b_width_engine_past_the_fused_attention_limit_matches_hf():
+    """max_len 16384 is more than any form of the fused attention launch holds (13360 positions at 64 x 64): the engine takes mode `fused`
+    (it used to take v3 and fail on its first step).  Its logits are those of the same decoder at max_len 4096 bit for bit -- the long
+    cache changes nothing -- and HF's within FUSED_7B_GATE."""
+    from quip_amd import decode, ops
+    dec, hf = _llama7b(16384)
+    assert 4096 < ops.decode_attention_fused_max_len(128, 64, 64) < 16384
+    toks, ref = hf_generate(hf, 7, NTOK)
+    eng = decode.DecodeEngine(dec, bs=1, max_len=16384)
+    assert eng.mode == "fused", eng.mode
+    got = _engine_logits(eng, [(toks, ref)])
+    short = decode.DecodeEngine(dec, bs=1, max_len=4096, mode="fused")
+    assert torch.equal(got, _engine_logits(short, [(toks, ref)]))
+    rel = _gate("llama7b-16k", got[:, 0], ref, toks, FUSED_7B_GATE)[0]
+    print(f"llama 7b width, max_len 16384, mode {eng.mode} vs HF: max-rel logits err {rel:.2e} (gate {FUSED_7B_GATE}); = max_len 4096 bit for bit")
