@@ -46,8 +46,17 @@ enum quipamd_dtype { QUIPAMD_F32 = 0, QUIPAMD_F16 = 1, QUIPAMD_BF16 = 2 };
  *            tiles of 64 lanes x 16 B in MFMA A-fragment order (oracle/quip_oracle.py
  *            pack_stream is the specification).  Requires m % 16 == 0, d % (512/bits) == 0. */
 /* bits = 3 with the STREAM layout: codes 0..7 stored in the 4-bit container (K2 dequantises nibbles; the 3-bit grid,
- * maxq = 7, is applied in its epilogue).  bits = 3 with the CANONICAL layout: the reference's 32-codes-in-3-words rule. */
-enum quipamd_layout { QUIPAMD_LAYOUT_CANONICAL = 0, QUIPAMD_LAYOUT_STREAM = 1 };
+ * maxq = 7, is applied in its epilogue).  bits = 3 with the CANONICAL layout: the reference's 32-codes-in-3-words rule.
+ * STREAM3 (opt-in, bits = 3 only): the same codes at exactly 3 bits per weight, m*d*3/32 words, m % 16 == 0, d % 256 == 0.  A code is split
+ *            into a 2-bit low plane (code & 3) and a 1-bit high plane (code >> 2).  Row tile rt (16 rows) is one contiguous run of
+ *            (d/256) * 1536 bytes made of 3072-byte blocks, one per PAIR of 256-column chunks: the two low tiles, each byte for byte the
+ *            2-bit STREAM tile of `code & 3` (64 lanes x 16 B, lane 16 g + j = row j, columns 32 t + 8 g + e of MFMA step t), then the
+ *            high bits of the two chunks, 64 lanes x 8 B each (an unpaired last chunk: its low tile, then its 512 B of high bits): the high
+ *            bit of step t, element e, field i = 4 (t & 1) + e / 2 of low dword u = t / 2, is bit 4 (i / 2) + 2 - SH[2 (u & 1) + (i & 1)]
+ *            (+ 16 for odd e) of high dword t / 4, SH = {0, -1, 2, 1}.  Every transfer unit is 16 bytes per lane and 16-byte aligned: one
+ *            64-lane transfer moves a low tile or the high bits of two chunks.  A pure permutation of the code bits; the NumPy
+ *            specification is tests/stream3_spec.py, the kernel that streams it csrc/dqgemm_w3.hip. */
+enum quipamd_layout { QUIPAMD_LAYOUT_CANONICAL = 0, QUIPAMD_LAYOUT_STREAM = 1, QUIPAMD_LAYOUT_STREAM3 = 2 };
 
 /* grid functions: quant.py:6-8 (a), quant.py:10-15 (b), quant.py:17-21 (c) */
 enum quipamd_qfn { QUIPAMD_QFN_A = 0, QUIPAMD_QFN_B = 1, QUIPAMD_QFN_C = 2 };
@@ -80,6 +89,9 @@ int quipamd_unpack(const int32_t *packed, int bits, int layout, uint8_t *codes, 
  * stream_out: m*d*cb/32 int32 words, cb = 4 for bits 3.  Needs m % 16 == 0 and d % (512/cb) == 0. */
 int quipamd_repack_canonical_to_stream(const int32_t *canonical, int bits, int32_t *stream_out, int64_t m, int64_t d,
                                        void *stream);
+/* The reference's 3-bit CANONICAL words (int32 [d/32*3, m]) -> STREAM3 (m*d*3/32 words): 3 bits in, 3 bits out, no expanded
+ * intermediate.  Needs m % 16 == 0 and d % 256 == 0.  quipamd_pack / quipamd_unpack take layout = STREAM3 with bits = 3. */
+int quipamd_repack_canonical_to_stream3(const int32_t *canonical, int32_t *stream3_out, int64_t m, int64_t d, void *stream);
 
 /* ---- K5: grid map / grid functions ---------------------------------------------------------
  * quipamd_qfnb_scale: scale = 2.4*sqrt(mean(W^2)) + 1e-16 evaluated in W's dtype
@@ -113,7 +125,10 @@ int quipamd_codes_to_weight(const uint8_t *codes, int qfn, const float *scale, c
  * x: [bs, d] bf16 or fp16 row-major (the reference widens x to fp32, quant.py:226-229: an fp16 model keeps its
  *    activation bits on the fp16 MFMA pipe, bf16 is for bf16 models); y: [bs, m] in y_dtype (x's dtype or F32).
  * accumulate != 0 (F32 y only): y += result, the reference's in-place contract (quant.py:226-230);
- * bias: float[m] or NULL.  Unlike the reference (single token only, quant.py:233) any bs >= 1. */
+ * bias: float[m] or NULL.  Unlike the reference (single token only, quant.py:233) any bs >= 1.
+ * layout = STREAM3 (bits = 3): the native 3-bit kernel family of csrc/dqgemm_w3.hip, a weight stream built for bs <= 16; larger batches
+ * are correct (16 rows per workgroup row, the weights streamed once per 16 rows) but not an MFMA-bound prefill kernel.  The grouped call
+ * takes STREAM3 as one launch per problem; quipamd_dequant_gemm_cfg with a non-zero cfg and STREAM3 fails with QUIPAMD_ERR_UNSUPPORTED. */
 int quipamd_dequant_gemm(const void *x, int x_dtype, const int32_t *qweight, int bits, int layout, int qfn,
                          const float *scale, const float *zero, const float *bias, void *y, int y_dtype,
                          int accumulate, int64_t bs, int64_t m, int64_t d, void *stream);

@@ -716,6 +716,20 @@ static int dequant_gemm_impl(int ngroups, const void *const *x, int x_dtype, con
     QA_REQUIRE(x_dtype == QUIPAMD_BF16 || x_dtype == QUIPAMD_F16, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: x must be bf16 or fp16");
     QA_REQUIRE(y_dtype == x_dtype || y_dtype == QUIPAMD_F32, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: y must be f32 or x's dtype");
     QA_REQUIRE(!accumulate || y_dtype == QUIPAMD_F32, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: accumulate needs f32 y");
+    if (layout == QUIPAMD_LAYOUT_STREAM3) {
+        // the native 3-bit layout has its own kernel family (dqgemm_w3.hip), taken on the layout value before anything below; a group is one
+        // launch per problem
+        for (int gi = 0; gi < ngroups; ++gi) {
+            K2Call c;                                                  // (pointers, qfn and shape are checked by k2w3_launch)
+            c.x = x[gi]; c.x_dtype = x_dtype; c.qweight = qweight[gi]; c.bits = bits; c.qfn = qfn; c.maxq = 7;
+            c.scale = scale[gi]; c.zero = zero ? zero[gi] : nullptr; c.bias = bias ? bias[gi] : nullptr; c.y = y[gi]; c.y_dtype = y_dtype;
+            c.accumulate = accumulate; c.bs = bs; c.m = m; c.d = d;
+            for (int i = 0; i < 4; ++i) c.cfg[i] = g_k2_cfg[i];
+            const int rc = k2w3_launch(c, stream);
+            if (rc != QUIPAMD_OK) return rc;
+        }
+        return QUIPAMD_OK;
+    }
     QA_REQUIRE(layout == QUIPAMD_LAYOUT_STREAM, QUIPAMD_ERR_UNSUPPORTED,
                "dequant_gemm: qweight must be in STREAM layout (repack with quipamd_unpack/quipamd_pack)");
     QA_REQUIRE(bits == 2 || bits == 3 || bits == 4, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: bits must be 2, 3 or 4");

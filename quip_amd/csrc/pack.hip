@@ -234,9 +234,121 @@ __global__ __launch_bounds__(256) void repack_stream_kernel(const uint32_t *__re
     out[gid] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// ---- STREAM3: 3-bit codes at 3 bits per weight, a 2-bit low plane and a 1-bit high plane (include/quip_amd.h; tests/stream3_spec.py is
+// the specification).  Row tile rt = nkc * 1536 contiguous bytes, per pair of chunks two low tiles (1 KiB each: the 2-bit STREAM tile of
+// code & 3) and 2 x 512 B of high bits;
+// thread = (row tile, chunk, lane): 4 low dwords + 2 high dwords.  The high bit of step t, element e sits where ONE shift of the high dword
+// drops it on bit 2 of its nibble in csrc/dqgemm_w3.hip's merge: n = 2 (u & 1) + (i & 1), left shift SH[n] = {0, -1, 2, 1}.
+__device__ __forceinline__ void stream3_pos(int t, int e, int &u, int &lsh, int &w, int &hbit)
+{
+    const int i = 4 * (t & 1) + (e >> 1), half = (e & 1) ? 16 : 0;
+    u = t >> 1;
+    lsh = 2 * i + half;
+    const int n = 2 * (u & 1) + (i & 1), sh = n == 0 ? 0 : n == 1 ? -1 : n == 2 ? 2 : 1;
+    w = t >> 2;
+    hbit = 4 * (i >> 1) + 2 - sh + half;
+}
+
+struct Stream3Index {
+    int64_t low, high, row, k0;        // uint4 index of the lane's low unit, uint2 index of its high unit, weight row, first column of the chunk
+    int g;
+};
+__device__ __forceinline__ bool stream3_index(int64_t gid, int64_t m, int64_t d, Stream3Index &ix)
+{
+    const int64_t nkc = d / 256;
+    if (gid >= (m / 16) * nkc * 64) return false;
+    const int lane = (int)(gid & 63);
+    const int64_t tile = gid >> 6, kc = tile % nkc, rt = tile / nkc;
+    // 1536 B per (row tile, chunk); chunk pair p at 3072 p: low tile, low tile, 512 B + 512 B of high bits; an unpaired last chunk: low tile, 512 B
+    const bool single = (nkc & 1) && kc == nkc - 1;
+    ix.low = rt * nkc * 96 + (kc >> 1) * 192 + (kc & 1) * 64 + lane;                                     // in 16-byte units
+    ix.high = rt * nkc * 192 + (kc >> 1) * 384 + (single ? 128 : 256 + (kc & 1) * 64) + lane;            // in 8-byte units
+    ix.row = rt * 16 + (lane & 15);
+    ix.g = lane >> 4;
+    ix.k0 = kc * 256;
+    return true;
+}
+// c8[t]: the 8 codes of step t, code e at bits [3 e, 3 e + 3)
+__device__ __forceinline__ void stream3_store(const uint32_t (&c8)[8], const Stream3Index &ix, uint32_t *out)
+{
+    uint32_t lo[4] = {0, 0, 0, 0}, hi[2] = {0, 0};
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            int u, lsh, w, hbit;
+            stream3_pos(t, e, u, lsh, w, hbit);
+            const uint32_t c = (c8[t] >> (3 * e)) & 7u;
+            lo[u] |= (c & 3u) << lsh;
+            hi[w] |= (c >> 2) << hbit;
+        }
+    reinterpret_cast<uint4 *>(out)[ix.low] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    reinterpret_cast<uint2 *>(out)[ix.high] = make_uint2(hi[0], hi[1]);
+}
+
+__global__ __launch_bounds__(256) void pack_stream3_kernel(const uint8_t *__restrict__ codes, uint32_t *__restrict__ out, int64_t m, int64_t d)
+{
+    Stream3Index ix;
+    if (!stream3_index((int64_t)blockIdx.x * blockDim.x + threadIdx.x, m, d, ix)) return;
+    const uint8_t *row = codes + ix.row * d + ix.k0 + 8 * ix.g;
+    uint32_t c8[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(row + 32 * t);
+        const uint32_t q[2] = {v.x, v.y};
+        c8[t] = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) c8[t] |= ((q[e >> 2] >> (8 * (e & 3))) & 7u) << (3 * e);
+    }
+    stream3_store(c8, ix, out);
+}
+
+__global__ __launch_bounds__(256) void unpack_stream3_kernel(const uint32_t *__restrict__ packed, uint8_t *__restrict__ codes, int64_t m, int64_t d)
+{
+    Stream3Index ix;
+    if (!stream3_index((int64_t)blockIdx.x * blockDim.x + threadIdx.x, m, d, ix)) return;
+    const uint4 lv = reinterpret_cast<const uint4 *>(packed)[ix.low];
+    const uint2 hv = reinterpret_cast<const uint2 *>(packed)[ix.high];
+    const uint32_t lo[4] = {lv.x, lv.y, lv.z, lv.w}, hi[2] = {hv.x, hv.y};
+    uint8_t *row = codes + ix.row * d + ix.k0 + 8 * ix.g;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        uint32_t q[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            int u, lsh, w, hbit;
+            stream3_pos(t, e, u, lsh, w, hbit);
+            q[e >> 2] |= (((lo[u] >> lsh) & 3u) | (((hi[w] >> hbit) & 1u) << 2)) << (8 * (e & 3));
+        }
+        *reinterpret_cast<uint2 *>(row + 32 * t) = make_uint2(q[0], q[1]);
+    }
+}
+
+// the reference's 3-bit checkpoint words (quant.py:192-220) -> STREAM3: the lane's 8 codes of step t are bits [24 g, 24 g + 24) of the 96-bit
+// group (k0 + 32 t) / 32 -- 3 bits in, 3 bits out, nothing expanded in memory
+__global__ __launch_bounds__(256) void repack_stream3_kernel(const uint32_t *__restrict__ canon, uint32_t *__restrict__ out, int64_t m, int64_t d)
+{
+    Stream3Index ix;
+    if (!stream3_index((int64_t)blockIdx.x * blockDim.x + threadIdx.x, m, d, ix)) return;
+    uint32_t c8[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int64_t grp = (ix.k0 + 32 * t) / 32;
+        c8[t] = bits96(canon[(grp * 3) * m + ix.row], canon[(grp * 3 + 1) * m + ix.row], canon[(grp * 3 + 2) * m + ix.row], 24 * ix.g, 24);
+    }
+    stream3_store(c8, ix, out);
+}
+
 int check_pack_args(const void *a, const void *b, int bits, int layout, int64_t m, int64_t d)
 {
     QA_REQUIRE((a && b) || m == 0 || d == 0, QUIPAMD_ERR_ARG, "pack/unpack: null pointer");
+    if (layout == QUIPAMD_LAYOUT_STREAM3) {
+        QA_REQUIRE(bits == 3, QUIPAMD_ERR_UNSUPPORTED, "pack/unpack: the STREAM3 layout holds 3-bit codes only (got %d)", bits);
+        QA_REQUIRE(m >= 0 && d >= 0, QUIPAMD_ERR_SHAPE, "pack/unpack: negative shape");
+        QA_REQUIRE(m % 16 == 0 && d % 256 == 0, QUIPAMD_ERR_SHAPE, "STREAM3 layout needs m %% 16 == 0 and d %% 256 == 0 (m=%lld d=%lld)",
+                   (long long)m, (long long)d);
+        return QUIPAMD_OK;
+    }
     QA_REQUIRE(bits == 2 || bits == 4 || (bits == 3 && layout == QUIPAMD_LAYOUT_CANONICAL), QUIPAMD_ERR_UNSUPPORTED,
                "pack/unpack: container bits must be 2 or 4, or 3 in the canonical layout (got %d)", bits);
     QA_REQUIRE(m >= 0 && d >= 0, QUIPAMD_ERR_SHAPE, "pack/unpack: negative shape");
@@ -271,6 +383,8 @@ extern "C" int quipamd_pack(const uint8_t *codes, int bits, int layout, int32_t 
     hipStream_t s = (hipStream_t)stream;
     if (layout == QUIPAMD_LAYOUT_CANONICAL && bits == 3) {
         pack3_canonical_kernel<<<qa_div_up((d / 32) * m, 256), 256, 0, s>>>(codes, (uint32_t *)packed, m, d);
+    } else if (layout == QUIPAMD_LAYOUT_STREAM3) {
+        pack_stream3_kernel<<<qa_div_up((m / 16) * (d / 256) * 64, 256), 256, 0, s>>>(codes, (uint32_t *)packed, m, d);
     } else if (layout == QUIPAMD_LAYOUT_CANONICAL) {
         const int64_t nwords = d / (32 / bits);
         dim3 grid(qa_div_up(nwords, TILE), qa_div_up(m, TILE));
@@ -295,6 +409,8 @@ extern "C" int quipamd_unpack(const int32_t *packed, int bits, int layout, uint8
     hipStream_t s = (hipStream_t)stream;
     if (layout == QUIPAMD_LAYOUT_CANONICAL && bits == 3) {
         unpack3_canonical_kernel<<<qa_div_up((d / 32) * m, 256), 256, 0, s>>>((const uint32_t *)packed, codes, m, d);
+    } else if (layout == QUIPAMD_LAYOUT_STREAM3) {
+        unpack_stream3_kernel<<<qa_div_up((m / 16) * (d / 256) * 64, 256), 256, 0, s>>>((const uint32_t *)packed, codes, m, d);
     } else if (layout == QUIPAMD_LAYOUT_CANONICAL) {
         const int64_t nwords = d / (32 / bits);
         dim3 grid(qa_div_up(nwords, TILE), qa_div_up(m, TILE));
@@ -326,5 +442,18 @@ extern "C" int quipamd_repack_canonical_to_stream(const int32_t *canonical, int 
     else if (bits == 3) repack_stream_kernel<3><<<qa_div_up(n, 256), 256, 0, s>>>((const uint32_t *)canonical, (uint4 *)stream_out, m, d);
     else repack_stream_kernel<4><<<qa_div_up(n, 256), 256, 0, s>>>((const uint32_t *)canonical, (uint4 *)stream_out, m, d);
     QA_LAUNCH_CHECK("quipamd_repack_canonical_to_stream");
+    return QUIPAMD_OK;
+}
+
+// The reference's 3-bit checkpoint (opt_pack3 -> Quant3Linear.pack, int32 [d/32*3, m]) -> STREAM3, the native 3-bit layout of
+// csrc/dqgemm_w3.hip: m*d*3/32 words in, m*d*3/32 words out.
+extern "C" int quipamd_repack_canonical_to_stream3(const int32_t *canonical, int32_t *stream3_out, int64_t m, int64_t d, void *stream)
+{
+    QA_REQUIRE((canonical && stream3_out) || m == 0 || d == 0, QUIPAMD_ERR_ARG, "repack: null pointer");
+    QA_REQUIRE(m >= 0 && d >= 0 && m % 16 == 0 && d % 256 == 0, QUIPAMD_ERR_SHAPE,
+               "repack: STREAM3 layout needs m %% 16 == 0 and d %% 256 == 0 (m=%lld d=%lld)", (long long)m, (long long)d);
+    if (m == 0 || d == 0) return QUIPAMD_OK;
+    repack_stream3_kernel<<<qa_div_up((m / 16) * (d / 256) * 64, 256), 256, 0, (hipStream_t)stream>>>((const uint32_t *)canonical, (uint32_t *)stream3_out, m, d);
+    QA_LAUNCH_CHECK("quipamd_repack_canonical_to_stream3");
     return QUIPAMD_OK;
 }

@@ -45,18 +45,21 @@ class collect_packed:
     """context manager: while it is active every `QuantMethod.free()` (the last call the reference's drivers make on a method,
     opt.py:166, llama.py:150) first turns the method's integer state into a packed `QuantLinear` (QuantLinear.from_method: codes,
     grid, rescale vector, operators -- what the reference throws away, method.py:223-225).  Methods without integer codes
-    (Nearest, GPTQ's general path) are skipped and stay dense.  `install(model)` swaps the collected layers into the model."""
+    (Nearest, GPTQ's general path) are skipped and stay dense.  `install(model)` swaps the collected layers into the model.
+    native3: layers quantised to 3 bits are packed in the STREAM3 layout (3 bits per weight) instead of the 4-bit container; ignored
+    for every other width."""
 
-    def __init__(self):
+    def __init__(self, native3=False):
+        self.native3 = native3
         self.layers = []          # [(the nn.Linear that was quantised, its QuantLinear)]
 
     def __enter__(self):
         self._orig = orig = _method.QuantMethod.free
-        got = self.layers
+        got, native3 = self.layers, self.native3
 
         def free(m):
             if getattr(m, 'codes', None) is not None and isinstance(m.layer, nn.Linear):
-                got.append((m.layer, QuantLinear.from_method(m, m.layer)))
+                got.append((m.layer, QuantLinear.from_method(m, m.layer, native3=native3)))
                 m.codes = None
             return orig(m)
         _method.QuantMethod.free = free

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 
-LAYOUT_CANONICAL, LAYOUT_STREAM = 0, 1
+LAYOUT_CANONICAL, LAYOUT_STREAM, LAYOUT_STREAM3 = 0, 1, 2       # STREAM3: 3-bit codes at 3 bits per weight (opt-in)
 QFN = {'a': 0, 'b': 1, 'c': 2}
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
@@ -42,6 +42,15 @@ def container_bits(bits):
     return 4 if bits == 3 else bits
 
 
+def packed_words(bits, layout, m, d):
+    """int32 words of a packed [m, d] weight: CANONICAL and STREAM3 store `bits` per code, STREAM the container's."""
+    if layout == LAYOUT_STREAM3:
+        if bits != 3:
+            raise ValueError(f"the STREAM3 layout holds 3-bit codes only (bits={bits})")
+        return m * d * 3 // 32
+    return m * d * (bits if layout == LAYOUT_CANONICAL else container_bits(bits)) // 32
+
+
 def stream_chunk(bits):
     """columns per 16-row STREAM tile (include/quip_amd.h)."""
     return 512 // container_bits(bits)
@@ -50,12 +59,12 @@ def stream_chunk(bits):
 # ------------------------------------------------------------------------------------------------- K1
 def pack(codes, bits, layout=LAYOUT_CANONICAL):
     """codes uint8 [m,d] -> int32 words; CANONICAL returns [d*bits/32, m] (zeroShot/models/quant.py:190-199; bits = 3: the
-    reference's 32-codes-in-3-words rule, quant.py:192-220)."""
+    reference's 32-codes-in-3-words rule, quant.py:192-220); STREAM: flat words of the container; STREAM3 (bits = 3): m*d*3/32 words."""
     _need_gpu(codes)
     assert codes.dtype == torch.uint8 and codes.dim() == 2
     codes = codes.contiguous()
     m, d = codes.shape
-    shape = (d * bits // 32, m) if layout == LAYOUT_CANONICAL else (m * d * container_bits(bits) // 32,)
+    shape = (d * bits // 32, m) if layout == LAYOUT_CANONICAL else (packed_words(bits, layout, m, d),)
     out = torch.empty(shape, dtype=torch.int32, device=codes.device)
     _lib.call("quipamd_pack", _p(codes), bits, layout, _p(out), m, d, _stream())
     return out
@@ -65,7 +74,7 @@ def unpack(packed, bits, layout, m, d):
     _need_gpu(packed)
     assert packed.dtype == torch.int32
     packed = packed.contiguous()
-    assert packed.numel() == m * d * (bits if layout == LAYOUT_CANONICAL else container_bits(bits)) // 32
+    assert packed.numel() == packed_words(bits, layout, m, d)
     codes = torch.empty((m, d), dtype=torch.uint8, device=packed.device)
     _lib.call("quipamd_unpack", _p(packed), bits, layout, _p(codes), m, d, _stream())
     return codes
@@ -79,6 +88,17 @@ def repack_canonical_to_stream(qweight, bits, m, d):
     qweight = qweight.contiguous()
     out = torch.empty(m * d * container_bits(bits) // 32, dtype=torch.int32, device=qweight.device)
     _lib.call("quipamd_repack_canonical_to_stream", _p(qweight), bits, _p(out), m, d, _stream())
+    return out
+
+
+def repack_canonical_to_stream3(qweight, m, d):
+    """a weight in the reference's 3-bit CANONICAL packing (int32 [d/32*3, m], Quant3Linear.pack) -> STREAM3 on the device: 3 bits per
+    weight in, 3 bits per weight out."""
+    _need_gpu(qweight)
+    assert qweight.dtype == torch.int32 and qweight.numel() == m * d * 3 // 32
+    qweight = qweight.contiguous()
+    out = torch.empty(m * d * 3 // 32, dtype=torch.int32, device=qweight.device)
+    _lib.call("quipamd_repack_canonical_to_stream3", _p(qweight), _p(out), m, d, _stream())
     return out
 
 
@@ -207,15 +227,15 @@ def codes_to_weight(codes, qfn, scale, zero, maxq, out_dtype=torch.float16):
 
 # ------------------------------------------------------------------------------------------------- K2
 def dequant_gemm(x, qweight, bits, qfn, scale, zero, bias, out=None, out_dtype=None, accumulate=False,
-                 m=None, cfg=None):
-    """y[bs,m] = x[bs,d] @ dequant(qweight)^T + bias; qweight in STREAM layout.  x: bf16 or fp16 (the MFMA runs in x's
+                 m=None, cfg=None, layout=LAYOUT_STREAM):
+    """y[bs,m] = x[bs,d] @ dequant(qweight)^T + bias; qweight in STREAM layout, or (bits = 3, layout=LAYOUT_STREAM3) in the native 3-bit one.  x: bf16 or fp16 (the MFMA runs in x's
     dtype); y: x's dtype (default) or fp32.  cfg = (family, p1, p2): force a kernel (include/quip_amd.h), for benchmarks."""
     _need_gpu(x, qweight)
     assert x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16), "x must be bf16 or fp16"
     x = x.contiguous()
     bs, d = x.shape
     if m is None:
-        m = qweight.numel() * 32 // container_bits(bits) // d
+        m = qweight.numel() * 32 // (3 if layout == LAYOUT_STREAM3 else container_bits(bits)) // d
     dev = x.device
     scale, zero = _grid(scale, zero, m, qfn, dev)
     bias = _f32vec(bias, dev)
@@ -226,18 +246,18 @@ def dequant_gemm(x, qweight, bits, qfn, scale, zero, bias, out=None, out_dtype=N
         out = torch.empty((bs, m), dtype=out_dtype or x.dtype, device=dev)
     assert out.is_contiguous() and out.shape == (bs, m)
     if cfg is None:
-        _lib.call("quipamd_dequant_gemm", _p(x), _dtype(x), _p(qweight), bits, LAYOUT_STREAM, QFN[qfn], _p(scale),
+        _lib.call("quipamd_dequant_gemm", _p(x), _dtype(x), _p(qweight), bits, layout, QFN[qfn], _p(scale),
                   _p(zero), _p(bias), _p(out), _dtype(out), int(bool(accumulate)), bs, m, d, _stream())
     else:
         c = (ctypes.c_int32 * 4)(*(list(cfg) + [0, 0, 0, 0])[:4])
-        _lib.call("quipamd_dequant_gemm_cfg", _p(x), _dtype(x), _p(qweight), bits, LAYOUT_STREAM, QFN[qfn], _p(scale),
+        _lib.call("quipamd_dequant_gemm_cfg", _p(x), _dtype(x), _p(qweight), bits, layout, QFN[qfn], _p(scale),
                   _p(zero), _p(bias), _p(out), _dtype(out), int(bool(accumulate)), bs, m, d,
                   ctypes.cast(c, ctypes.c_void_p), _stream())
     return out
 
 
-def dequant_gemm_grouped(xs, qweights, bits, qfn, scales, zeros, outs, m):
-    """ngroups <= 4 problems of identical shape in one launch: xs[i] [bs,d] bf16, outs[i] [bs,m] (fp32 or bf16)."""
+def dequant_gemm_grouped(xs, qweights, bits, qfn, scales, zeros, outs, m, layout=LAYOUT_STREAM):
+    """ngroups <= 4 problems of identical shape (and layout) in one call: xs[i] [bs,d] bf16 / fp16, outs[i] [bs,m] (fp32 or x's dtype)."""
     n = len(xs)
     bs, d = xs[0].shape
     vp = ctypes.c_void_p
@@ -245,7 +265,7 @@ def dequant_gemm_grouped(xs, qweights, bits, qfn, scales, zeros, outs, m):
         _f32ptr(t, "scale / zero")
     arr = lambda ts: (vp * n)(*[vp(0 if t is None else t.data_ptr()) for t in ts])
     zs = arr(zeros) if zeros is not None and zeros[0] is not None else None
-    _lib.call("quipamd_dequant_gemm_grouped", n, arr(xs), _dtype(xs[0]), arr(qweights), bits, LAYOUT_STREAM, QFN[qfn], arr(scales),
+    _lib.call("quipamd_dequant_gemm_grouped", n, arr(xs), _dtype(xs[0]), arr(qweights), bits, layout, QFN[qfn], arr(scales),
               zs, None, arr(outs), _dtype(outs[0]), 0, bs, m, d, _stream())
     return outs
 

@@ -167,11 +167,16 @@ class QuantLinear(nn.Module):
 
     where What2 = dequant(codes) lives in the projected basis.  forward() accepts any batch shape."""
 
-    def __init__(self, infeatures, outfeatures, bits=2, qfn='b'):
+    def __init__(self, infeatures, outfeatures, bits=2, qfn='b', native3=False):
         super().__init__()
-        assert bits in (2, 3, 4)                  # 3-bit codes (--wbits 3) are stored in the 4-bit container
+        assert bits in (2, 3, 4)                  # 3-bit codes (--wbits 3) are stored in the 4-bit container, or with native3 at 3 bits
+        if native3 and (bits != 3 or infeatures % 256 != 0 or outfeatures % 16 != 0):
+            raise ValueError(f"native3 is the STREAM3 layout of 3-bit codes: needs bits == 3, infeatures % 256 == 0 and outfeatures % 16 == 0 "
+                             f"(bits={bits}, {infeatures} -> {outfeatures})")
         self.infeatures, self.outfeatures, self.bits, self.qfn = infeatures, outfeatures, bits, qfn
-        self.register_buffer('qweight', torch.zeros(infeatures * outfeatures * ops.container_bits(bits) // 32, dtype=torch.int32))
+        # layout of `qweight`: STREAM (3-bit codes in the 4-bit container) or, opt-in, STREAM3 (3 bits per weight, csrc/dqgemm_w3.hip)
+        self.layout = ops.LAYOUT_STREAM3 if native3 else ops.LAYOUT_STREAM
+        self.register_buffer('qweight', torch.zeros(ops.packed_words(bits, self.layout, outfeatures, infeatures), dtype=torch.int32))
         self.register_buffer('scales', torch.zeros(1 if qfn == 'b' else outfeatures))
         self.register_buffer('zeros', torch.zeros(outfeatures) if qfn != 'b' else None)
         self.register_buffer('bias', None)
@@ -181,6 +186,7 @@ class QuantLinear(nn.Module):
         self._drop_derived()
 
     _F32_BUFFERS = ('scales', 'zeros', 'bias', 'inv_scaleWH')
+    layout = ops.LAYOUT_STREAM        # (class default: a module pickled before the STREAM3 layout existed holds the container)
 
     def _apply(self, fn, recurse=True):
         """model.half() / .to(dtype) must not narrow the grid parameters: the kernels read them as float32 (and fp16 could
@@ -216,7 +222,7 @@ class QuantLinear(nn.Module):
         # what the decode launches derive from the packed state (decode_qweight, bias16, the layer-pair tables) is rebuilt on next use;
         # tables other layers keep about THIS one are keyed by its generation
         self._drop_derived()
-        self.qweight = ops.pack(codes, self.bits, ops.LAYOUT_STREAM)
+        self.qweight = ops.pack(codes, self.bits, self.layout)
         self.scales = scale.to(dev, torch.float32).reshape(-1).clone()
         self.zeros = None if zero is None else zero.to(dev, torch.float32).reshape(-1).clone()
         self.bias = None if bias is None else bias.detach().to(dev, torch.float32).clone()
@@ -236,8 +242,28 @@ class QuantLinear(nn.Module):
         QuantLinear._GEN[0] += 1
         self.__dict__['_pack_gen'] = QuantLinear._GEN[0]
 
+    @property
+    def native3(self):
+        return self.layout == ops.LAYOUT_STREAM3
+
+    @torch.no_grad()
+    def to_native3(self):
+        """convert a packed 3-bit layer from the 4-bit container to STREAM3 in place, on the device (unpack -> pack): 25 % fewer resident
+        bytes, the same codes.  Returns self; a layer that is native already is left alone."""
+        if self.native3:
+            return self
+        if self.bits != 3 or self.infeatures % 256 != 0 or self.outfeatures % 16 != 0:
+            raise ValueError(f"to_native3: needs a 3-bit layer with infeatures % 256 == 0 (bits={self.bits}, {self.infeatures} -> {self.outfeatures})")
+        if self.qweight.numel() == 0 and self.infeatures * self.outfeatures:
+            raise RuntimeError("QuantLinear.decode_only() dropped the natural-order codes: nothing to convert")
+        codes = ops.unpack(self.qweight, 3, ops.LAYOUT_STREAM, self.outfeatures, self.infeatures)
+        self._drop_derived()
+        self.layout = ops.LAYOUT_STREAM3
+        self.qweight = ops.pack(codes, 3, ops.LAYOUT_STREAM3)
+        return self
+
     def packed_bytes(self):
-        """bytes of codes this layer holds on its device: the STREAM words, plus the decode-order copy once a fused decode launch built it"""
+        """bytes of codes this layer holds on its device: the STREAM / STREAM3 words, plus the decode-order copy once a fused decode launch built it"""
         qd = self.__dict__.get('_qweight_d')
         return self.qweight.numel() * 4 + (0 if qd is None else qd.numel() * 4)
 
@@ -251,14 +277,16 @@ class QuantLinear(nn.Module):
 
     @classmethod
     @torch.no_grad()
-    def from_method(cls, method, layer):
+    def from_method(cls, method, layer, native3=False):
         """Packed layer from a Balance (or any QuantMethod that kept integer codes) AFTER fasterquant() and BEFORE
         free(): codes + grid parameters in the projected basis, plus the rescale vector and the structured operators
         of QuantMethod.preproc -- the state the reference throws away (vector_balance.py:528-530, method.py:223-225)."""
         codes = method.codes
         bits = int(torch.log2(method.quantizer.maxq.float() + 1).round().item())
         qfn = method.quantizer.qfn if method.quantizer.qfn in ('a', 'b') else 'a'
-        ql = cls(codes.shape[1], codes.shape[0], bits=bits, qfn=qfn)
+        # native3: the STREAM3 layout where the method quantised to 3 bits and the shape allows it; ignored otherwise
+        native3 = bool(native3) and bits == 3 and codes.shape[1] % 256 == 0 and codes.shape[0] % 16 == 0
+        ql = cls(codes.shape[1], codes.shape[0], bits=bits, qfn=qfn, native3=native3)
         U = getattr(method, '_U', None) if getattr(method, 'preproc_proj', False) else None
         V = getattr(method, '_V', None) if getattr(method, 'preproc_proj', False) else None
         sWH = method.scaleWH if getattr(method, 'preproc_rescale', False) else None
@@ -274,7 +302,7 @@ class QuantLinear(nn.Module):
             if self.qweight.numel() == 0:
                 raise RuntimeError("QuantLinear.decode_only() dropped the natural-order codes: re-pack the layer to rebuild its decode copy")
             m, d = self.outfeatures, self.infeatures
-            codes = ops.unpack(self.qweight, self.bits, ops.LAYOUT_STREAM, m, d)
+            codes = ops.unpack(self.qweight, self.bits, self.layout, m, d)
             if self.U is not None and self.U.fold_ok:         # (an operator no decode launch can run keeps the natural order: its side
                 perm = torch.empty(m, dtype=torch.int64, device=codes.device)   #  is served by the K3 kernels)
                 perm[self.U.zt_rows()] = torch.arange(m, device=codes.device)          # new row r holds old row perm[r]
@@ -283,6 +311,7 @@ class QuantLinear(nn.Module):
                 perm = torch.empty(d, dtype=torch.int64, device=codes.device)
                 perm[self.V.image_cols()] = torch.arange(d, device=codes.device)
                 codes = codes[:, perm]
+            # (always the container the fused decode launches read, also for a native3 layer: the same words either way)
             qd = ops.pack(codes.contiguous(), self.bits, ops.LAYOUT_STREAM)
             self.__dict__['_qweight_d'] = qd
         return qd
@@ -300,18 +329,20 @@ class QuantLinear(nn.Module):
 
     def packed_state(self):
         """everything needed to rebuild the layer, as CPU tensors / plain Python (the packed checkpoint record):
-        STREAM-layout codes, grid parameters, bias, 1/scaleWH and the generator tuples of U and V."""
+        STREAM-layout codes (or STREAM3: "layout"), grid parameters, bias, 1/scaleWH and the generator tuples of U and V."""
         if self.qweight.numel() == 0 and self.infeatures * self.outfeatures:
             raise RuntimeError("QuantLinear.decode_only() dropped the natural-order codes this record is made of: save the packed checkpoint first")
         cpu = lambda t: None if t is None else t.detach().cpu()
         return {"infeatures": self.infeatures, "outfeatures": self.outfeatures, "bits": self.bits, "qfn": self.qfn,
-                "qweight": cpu(self.qweight), "scales": cpu(self.scales), "zeros": cpu(self.zeros), "bias": cpu(self.bias),
+                "layout": self.layout, "qweight": cpu(self.qweight), "scales": cpu(self.scales), "zeros": cpu(self.zeros), "bias": cpu(self.bias),
                 "inv_scaleWH": cpu(self.inv_scaleWH),
                 "U": None if self.U is None else self.U.state(), "V": None if self.V is None else self.V.state()}
 
     @classmethod
     def from_packed_state(cls, st, device):
-        ql = cls(st["infeatures"], st["outfeatures"], bits=st["bits"], qfn=st["qfn"])
+        # a record without "layout" was written before STREAM3 existed: the container
+        ql = cls(st["infeatures"], st["outfeatures"], bits=st["bits"], qfn=st["qfn"],
+                 native3=st.get("layout", ops.LAYOUT_STREAM) == ops.LAYOUT_STREAM3)
         dev = lambda t: None if t is None else t.to(device)
         ql.qweight, ql.scales, ql.zeros = dev(st["qweight"]), dev(st["scales"]), dev(st["zeros"])
         ql.bias, ql.inv_scaleWH = dev(st["bias"]), dev(st["inv_scaleWH"])
@@ -347,10 +378,10 @@ class QuantLinear(nn.Module):
                 xt = (x2.float() * self.inv_scaleWH).to(adt)
         if self.U is None:
             y = ops.dequant_gemm(xt, self.qweight, self.bits, self.qfn, self.scales, self.zeros, self.bias,
-                                 out_dtype=torch.float32, m=self.outfeatures)
+                                 out_dtype=torch.float32, m=self.outfeatures, layout=self.layout)
         else:
             y = ops.dequant_gemm(xt, self.qweight, self.bits, self.qfn, self.scales, self.zeros, None,
-                                 out_dtype=torch.float32, m=self.outfeatures)
+                                 out_dtype=torch.float32, m=self.outfeatures, layout=self.layout)
             y = self.U.apply_rows(y, transpose=True, out_dtype=x.dtype, bias=self.bias, fast16=few)   # fp32 in, caller's dtype out
         return y.to(x.dtype).reshape(*shape[:-1], self.outfeatures)
 
@@ -360,10 +391,12 @@ class Quant3Linear(QuantLinear):
     `Quant3Linear(infeatures, outfeatures)`, `.pack(linear, scales, zeros)` from a fake-quantised nn.Linear and its
     per-row grid (qfn a), `forward(x)` = bias + sum (scales q - zeros scales) x.  Differences: the codes live on the GPU
     in the 4-bit STREAM container that K2 reads (the reference's 32-codes-in-3-words array had no runnable kernel,
-    quant.py:166-169), and forward() accepts any batch, not only a single token (quant.py:233)."""
+    quant.py:166-169), and forward() accepts any batch, not only a single token (quant.py:233).
+    native3=True: the codes are held at 3 bits per weight in the STREAM3 layout (25 % fewer resident bytes, its own K2 kernel); a
+    reference checkpoint is repacked 3 bits -> 3 bits on the device."""
 
-    def __init__(self, infeatures, outfeatures):
-        super().__init__(infeatures, outfeatures, bits=3, qfn='a')
+    def __init__(self, infeatures, outfeatures, native3=False):
+        super().__init__(infeatures, outfeatures, bits=3, qfn='a', native3=native3)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         """A checkpoint written by the REFERENCE's Quant3Linear (opt.py:303-315 opt_pack3, quant.py:176-197) loads as it is:
@@ -389,7 +422,7 @@ class Quant3Linear(QuantLinear):
                         if prefix + k in missing:
                             missing.remove(prefix + k)
                 return
-            conv = reference_packed_buffers(qw, sc, zr, 3, self.infeatures, self.outfeatures, self.qweight.device)
+            conv = reference_packed_buffers(qw, sc, zr, 3, self.infeatures, self.outfeatures, self.qweight.device, native3=self.native3)
             state_dict[prefix + 'qweight'], state_dict[prefix + 'scales'], state_dict[prefix + 'zeros'] = conv
             if b is not None:                                # only after every shape check above has passed
                 self.bias = torch.zeros(self.outfeatures, device=self.qweight.device)
@@ -402,7 +435,8 @@ class Quant3Linear(QuantLinear):
         if pend is not None and self.qweight.device.type == 'cuda':
             qw, sc, zr, b = pend
             dev = self.qweight.device
-            self.qweight, self.scales, self.zeros = reference_packed_buffers(qw, sc, zr, 3, self.infeatures, self.outfeatures, dev)
+            self.qweight, self.scales, self.zeros = reference_packed_buffers(qw, sc, zr, 3, self.infeatures, self.outfeatures, dev,
+                                                                             native3=self.native3)
             self.bias = None if b is None else b.to(dev, torch.float32).reshape(-1).clone()
             self._reference_pending = None
         return self
@@ -429,33 +463,36 @@ class Quant3Linear(QuantLinear):
 _DEV = 'cuda:0'
 
 
-def reference_packed_buffers(qweight, scales, zeros, bits, infeatures, outfeatures, device):
+def reference_packed_buffers(qweight, scales, zeros, bits, infeatures, outfeatures, device, native3=False):
     """(qweight, scales, zeros) of a layer packed by the reference -- Quant3Linear.pack (quant.py:185-220: [in/32*3, out])
     or Quant4Linear (zeroShot/models/quant.py:183-199: [in/8, out]), zeros = zero * scale -- as the buffers QuantLinear keeps:
-    STREAM-layout codes (repacked on the device), per-row scale, integer zero."""
+    STREAM-layout codes (repacked on the device; native3: 3-bit words straight into STREAM3), per-row scale, integer zero."""
     device = torch.device(device)
     if device.type != 'cuda':
         raise RuntimeError("a reference-format checkpoint is repacked on the GPU: move the module to the device first "
                            "(there is no CPU fallback)")
     assert tuple(qweight.shape) == (infeatures * bits // 32, outfeatures), "not the reference's [in*bits/32, out] packing"
-    qs = ops.repack_canonical_to_stream(qweight.to(device=device, dtype=torch.int32), bits, outfeatures, infeatures)
+    if native3 and bits != 3:
+        raise ValueError("native3 is the STREAM3 layout of 3-bit codes")
+    qw = qweight.to(device=device, dtype=torch.int32)
+    qs = ops.repack_canonical_to_stream3(qw, outfeatures, infeatures) if native3 else ops.repack_canonical_to_stream(qw, bits, outfeatures, infeatures)
     sc = scales.to(device, torch.float32).reshape(-1)
     zs = zeros.to(device, torch.float32).reshape(-1)
     zi = torch.where(sc != 0, zs / sc, torch.zeros_like(zs)).round()          # zeros = zero * scale, zero an integer
     return qs, sc.clone(), zi
 
 
-def from_reference_packed(qweight, scales, zeros, bias, bits, device=_DEV):
+def from_reference_packed(qweight, scales, zeros, bias, bits, device=_DEV, native3=False):
     """QuantLinear (qfn a) from the buffers of a reference-packed layer (3 or 4 bit, see reference_packed_buffers)."""
     outfeatures = qweight.shape[1]
     infeatures = qweight.shape[0] * 32 // bits
-    ql = (Quant3Linear(infeatures, outfeatures) if bits == 3 else QuantLinear(infeatures, outfeatures, bits=bits, qfn='a')).to(device)
-    ql.qweight, ql.scales, ql.zeros = reference_packed_buffers(qweight, scales, zeros, bits, infeatures, outfeatures, device)
+    ql = (Quant3Linear(infeatures, outfeatures, native3=native3) if bits == 3 else QuantLinear(infeatures, outfeatures, bits=bits, qfn='a', native3=native3)).to(device)
+    ql.qweight, ql.scales, ql.zeros = reference_packed_buffers(qweight, scales, zeros, bits, infeatures, outfeatures, device, native3=native3)
     ql.bias = None if bias is None else bias.detach().to(device, torch.float32).reshape(-1).clone()
     return ql
 
 
-def make_quant3(module, names, name=''):
+def make_quant3(module, names, name='', native3=False):
     """replace the named nn.Linear children by (empty) Quant3Linear layers, to be filled by .pack() or a state dict
     (quant.py:236-246)."""
     if isinstance(module, Quant3Linear):
@@ -463,9 +500,9 @@ def make_quant3(module, names, name=''):
     for attr, tmp in list(module.named_children()):       # the reference walks dir(module); children cover containers too
         name1 = name + '.' + attr if name != '' else attr
         if name1 in names:
-            setattr(module, attr, Quant3Linear(tmp.in_features, tmp.out_features))
+            setattr(module, attr, Quant3Linear(tmp.in_features, tmp.out_features, native3=native3))
     for name1, child in module.named_children():
-        make_quant3(child, names, name + '.' + name1 if name != '' else name1)
+        make_quant3(child, names, name + '.' + name1 if name != '' else name1, native3=native3)
 
 
 def _ln_params(ln):
@@ -526,13 +563,15 @@ def packed_forward_fused(qls, x, ln=None, residual=None, relu=False, gate_up=Non
                   and x.is_contiguous() and gate_up.is_contiguous())
         if not (in_kernel or in_blk):
             x, gate_up = torch.nn.functional.silu(x) * gate_up, None
-    same = len({(q.infeatures, q.outfeatures, q.bits) for q in qls}) == 1
+    # (the layout is part of the key: a native3 layer's words must never reach a kernel that reads the container; a group of mixed layouts
+    #  is split into one-layout subgroups or takes the per-layer forward below, so launch 2 always sees ONE layout)
+    same = len({(q.infeatures, q.outfeatures, q.bits, q.layout) for q in qls}) == 1
     if not same and gate_up is None and all(q.U is not None and q.V is not None and q.qfn == 'b' for q in qls) and rows <= ops.OrthoOp.SMALL_ROWS:
         # layers of different shapes on one input (grouped-query attention: q [h] beside k, v [kv_heads * hd]): each equal-shape
         # subgroup takes the three-launch form on its own
         groups = {}
         for i, q in enumerate(qls):
-            groups.setdefault((q.infeatures, q.outfeatures, q.bits), []).append(i)
+            groups.setdefault((q.infeatures, q.outfeatures, q.bits, q.layout), []).append(i)
         outs = [None] * len(qls)
         for idx in groups.values():
             for i, o in zip(idx, packed_forward_fused([qls[i] for i in idx], x, ln=ln, residual=residual, relu=relu)):
@@ -587,7 +626,7 @@ def packed_forward_fused(qls, x, ln=None, residual=None, relu=False, gate_up=Non
         xts = [q.V.apply_rows(h, colscale=q.inv_scaleWH, out_dtype=torch.bfloat16) for q in qls]
     # launch 2
     ys = [torch.empty((rows, m), dtype=torch.float32, device=dev) for _ in qls]
-    ops.dequant_gemm_grouped(xts, [q.qweight for q in qls], qls[0].bits, 'b', [q.scales for q in qls], None, ys, m)
+    _grouped_gemm(qls, xts, ys, m)
     # launch 3
     res = None if residual is None else residual.contiguous()
     if all(fast(q.U, None) for q in qls):
@@ -643,11 +682,21 @@ def packed_vgemm_stage(qls, x, ln=None):
     return ys
 
 
+def _grouped_gemm(qls, xts, ys, m):
+    """y_i = What_i xt_i for layers of one shape: one grouped call when they share the layout of their words, else one call per layer,
+    each with its own layout (the second branch is reached from packed_gemm_stage only: packed_forward_fused never hands over a mixed group)"""
+    if len({q.layout for q in qls}) == 1:
+        ops.dequant_gemm_grouped(xts, [q.qweight for q in qls], qls[0].bits, 'b', [q.scales for q in qls], None, ys, m, layout=qls[0].layout)
+        return
+    for q, xt, y in zip(qls, xts, ys):
+        ops.dequant_gemm_grouped([xt], [q.qweight], q.bits, 'b', [q.scales], None, [y], m, layout=q.layout)
+
+
 def packed_gemm_stage(qls, xts):
     """launch 2: y_i = What_i xt_i (grouped fused dequant-GEMM, fp32)."""
     rows, m = xts[0].shape[0], qls[0].outfeatures
     ys = [torch.empty((rows, m), dtype=torch.float32, device=xts[0].device) for _ in qls]
-    ops.dequant_gemm_grouped(xts, [q.qweight for q in qls], qls[0].bits, 'b', [q.scales for q in qls], None, ys, m)
+    _grouped_gemm(qls, xts, ys, m)
     return ys
 
 
