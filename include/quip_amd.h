@@ -589,7 +589,8 @@ int quipamd_gptq_round_groups(const float *W_rev, const float *FT, int bits, int
 int quipamd_gptq_feedback(const float *H, float *FT, float *work, int64_t d, int *info, void *stream);
 
 /* X = (I + N)^-1 for a strictly-upper-triangular N (only the strict upper part of N is read; X comes back upper
- * triangular with a unit diagonal, its strict lower part is NOT written).  N, X, work: three distinct float [d, d]. */
+ * triangular with a unit diagonal: its 128 x 128 diagonal blocks are written whole, zeros below the diagonal, the
+ * blocks below them are NOT written).  N, X, work: three distinct float [d, d]. */
 int quipamd_unit_upper_inverse(const float *N, float *X, float *work, int64_t d, void *stream);
 
 /* One greedy coordinate-descent pass of LDLQ's post-processing (round_ldl / round_ldl_block with n_greedy_passes > 0,
