@@ -1,4 +1,4 @@
-"""ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h).
+"""ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h and include/quip_amd_prefill.h).
 
 The product path has no CPU fallback: if the shared library is missing or a symbol is absent, importing the
 ops fails loudly here.  Build it with `python __graft_entry__.py` (hipcc --offload-arch=gfx950).
@@ -97,6 +97,13 @@ SIGNATURES = {
                                          c_float, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],
 }
 
+# the prompt-side entries: include/quip_amd_prefill.h (its opening comment says why they are a table of their own); tests/test_prefill_host.py
+# checks this table against that header and tests/test_gpu_prefill_contract.py runs every launching name of it under a guard arena
+PREFILL_SIGNATURES = {
+    "quipamd_prefill_attention": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_int, c_i64,
+                                  c_float, c_i64, c_i64, c_i64, c_vp],
+}
+
 _lib = None
 
 
@@ -123,6 +130,13 @@ def load():
                                                                                                       "quipamd_dequant_gemm_grouped_config", "quipamd_decode_attention_config") else
                       c_i64 if name in ("quipamd_hessian_fast_workspace", "quipamd_vecquant_workspace_bytes", "quipamd_gptq_qfnb_workspace_bytes", "quipamd_gptq_qfnb_info_offset", "quipamd_preproc_workspace_bytes",
                                                           "quipamd_decode_attention_grouped_workspace_bytes", "quipamd_decode_attention_fused_max_len") else c_int)
+    for name, argtypes in PREFILL_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise QuipAmdError(f"{LIB_PATH} does not export {name}; rebuild it") from e
+        fn.argtypes = argtypes
+        fn.restype = c_int
     _lib = lib
     return lib
 

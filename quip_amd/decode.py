@@ -128,6 +128,16 @@ class OPTBlock(nn.Module):
         return x
 
 
+    def prefill(self, x, kc, vc, start, T):
+        """T new positions per sequence in one pass: x [bs*T, h] (row b*T + t), start int64 [1] on the device.  The projections run through
+        the layers' own forward (K3 row operators + the batched K2 kernel for packed layers), the attention is ops.prefill_attention."""
+        hn = self.ln1(x)
+        q, k, v = self.q_proj(hn), self.k_proj(hn), self.v_proj(hn)
+        o = ops.prefill_attention(q, k, v, kc, vc, start, T)
+        x = x + self.out_proj(o)
+        return x + self.fc2(F.relu(self.fc1(self.ln2(x))))
+
+
 class OPTDecoder(nn.Module):
     """token + learned position embedding (offset 2), the blocks, final LayerNorm, head (tied to the embedding unless given)"""
     arch = "opt"
@@ -230,6 +240,18 @@ class OPTDecoder(nn.Module):
             prev = blk.fc2
         return prev, y2, x
 
+    def prefill(self, ids, pos, caches, arange, all_logits=False):
+        """ids int64 [bs, T] at cache positions pos .. pos + T - 1 (pos int64 [1] on the device, not advanced here); returns the logits of
+        the last position [bs, vocab], or of every position [bs, T, vocab]"""
+        bs, T = ids.shape
+        x = self.tok(ids) + F.embedding(arange[:T] + pos + 2, self.posemb.weight)        # learned positions start + t + 2
+        x = x.reshape(bs * T, self.h)
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            x = blk.prefill(x, kc, vc, pos, T)
+        if all_logits:
+            return self.head(x).view(bs, T, -1)
+        return self.head(x.view(bs, T, self.h)[:, -1])
+
     def step(self, ids, pos, caches, arange):
         """one token for every batch row: ids int64 [bs], pos int64 [1]; returns logits [bs, vocab]."""
         x = self.embed(ids, pos)
@@ -291,6 +313,17 @@ class LlamaBlock(nn.Module):
             x = packed_forward_fused([self.o_proj], o, residual=x)[0]
             g, u = packed_forward_fused([self.gate_proj, self.up_proj], x, ln=self.n2)
             return packed_forward_fused([self.down_proj], g, residual=x, gate_up=u)[0]       # silu(g) * u formed inside the V launch
+        x = x + self.o_proj(o)
+        hn = self.n2(x)
+        return x + self.down_proj(F.silu(self.gate_proj(hn)) * self.up_proj(hn))
+
+
+    def prefill(self, x, kc, vc, start, T, cos, sin):
+        """T new positions per sequence in one pass: x [bs*T, h] (row b*T + t), start int64 [1] on the device; rotary, cache append and
+        causal attention are ops.prefill_attention (multi-head and grouped-query alike)"""
+        hn = self.n1(x)
+        q, k, v = self.q_proj(hn), self.k_proj(hn), self.v_proj(hn)
+        o = ops.prefill_attention(q, k, v, kc, vc, start, T, cos, sin)
         x = x + self.o_proj(o)
         hn = self.n2(x)
         return x + self.down_proj(F.silu(self.gate_proj(hn)) * self.up_proj(hn))
@@ -403,6 +436,17 @@ class LlamaDecoder(nn.Module):
             yd = fused_bigp_tail(gu, blk.down_proj, ygu)                       # fp32 accumulator, ZT order of down_proj's U
             prev = blk.down_proj
         return prev, yd, x
+
+    def prefill(self, ids, pos, caches, arange, all_logits=False):
+        """ids int64 [bs, T] at cache positions pos .. pos + T - 1 (pos int64 [1] on the device, not advanced here); returns the logits of
+        the last position [bs, vocab], or of every position [bs, T, vocab]"""
+        bs, T = ids.shape
+        x = self.tok(ids).reshape(bs * T, self.h)
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            x = blk.prefill(x, kc, vc, pos, T, self.cos, self.sin)
+        if all_logits:
+            return self.head(x).view(bs, T, -1)
+        return self.head(x.view(bs, T, self.h)[:, -1])
 
     def step(self, ids, pos, caches, arange):
         x = self.embed(ids, pos)
@@ -586,10 +630,97 @@ class DecodeEngine:
         self.step()
         return self.logits
 
+    PREFILL_BYTES = 64 << 20       # default chunk: the widest activation of a pass (bs * chunk rows of the feed-forward width) stays under this
+
+    def _ffn_width(self):
+        b = self.dec.blocks[0]
+        lin = b.fc1 if hasattr(b, "fc1") else b.gate_proj
+        return getattr(lin, "out_features", None) or lin.outfeatures
+
+    def prefill_chunk(self):
+        """the default `chunk` of prefill(): the most positions per sequence (a multiple of 64, the attention kernel's query tile) for which
+        the feed-forward activation [bs * chunk, ffn] of a pass stays within PREFILL_BYTES; at least 64"""
+        item = torch.empty((), dtype=self.dtype).element_size()
+        rows = self.PREFILL_BYTES // (self._ffn_width() * item * self.bs)
+        return max(64, rows // 64 * 64)
+
+    @torch.no_grad()
+    def prefill(self, prompt_ids, chunk=None, all_logits=False):
+        """feed a whole prompt, int64 [bs, n] with n >= 1, in passes of at most `chunk` positions per sequence (default: prefill_chunk()):
+        every block's cache rows pos .. pos + n - 1 are written and the engine advances by n.  The logits of the last prompt position are
+        left in `logits` and their argmax in `ids`, so step() / generate() continue from the prompt by graph replay.  On an engine that
+        already holds positions the prompt continues the sequence.  Returns `logits` [bs, vocab], or with all_logits the logits of every
+        prompt position [bs, n, vocab].  Raises before anything is written when the prompt does not fit the cache, bs is wrong, or a layer
+        dropped its natural-order codes (QuantLinear.decode_only)."""
+        if not torch.is_tensor(prompt_ids) or prompt_ids.dim() != 2 or prompt_ids.shape[0] != self.bs or prompt_ids.shape[1] < 1:
+            shape = tuple(prompt_ids.shape) if torch.is_tensor(prompt_ids) else type(prompt_ids).__name__
+            raise ValueError(f"DecodeEngine.prefill: prompt_ids must be int64 [bs = {self.bs}, n >= 1] (got {shape})")
+        n = prompt_ids.shape[1]
+        if self._steps + n > self.max_len:
+            raise RuntimeError(f"DecodeEngine.prefill: a prompt of {n} positions does not fit the KV cache ({self._steps} of max_len "
+                               f"{self.max_len} positions are in use)")
+        for name, m in self.dec.named_modules():
+            if isinstance(m, QuantLinear) and m.qweight.numel() == 0 and m.infeatures * m.outfeatures:
+                raise RuntimeError(f"DecodeEngine.prefill: layer {name} went through QuantLinear.decode_only(): it kept the decode-order codes "
+                                   "only, and the prompt pass runs the layers' forward on the natural-order codes.  Build the engine from the "
+                                   "packed checkpoint without decode_only() (or re-pack the layer), or feed the prompt token by token with forward()")
+        if chunk is None:
+            chunk = self.prefill_chunk()
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("DecodeEngine.prefill: chunk must be at least 1")
+        self._prepare()                                  # (its warm-up and capture steps write position 0 and reset: before the first cache write)
+        ids = prompt_ids.to(device=self.dev, dtype=torch.int64)
+        outs = []
+        for lo in range(0, n, chunk):
+            part = ids[:, lo:lo + chunk]
+            lg = self.dec.prefill(part, self.pos, self.caches, self.arange, all_logits=all_logits)
+            self.pos.add_(part.shape[1])                 # the next pass starts behind this one: `start` lives on the device
+            if all_logits:
+                outs.append(lg)
+        last = lg[:, -1] if all_logits else lg
+        self.logits.copy_(last)
+        ops.argmax_rows(self.logits, out=self.ids)
+        if self._fh:
+            self.part_idx.fill_(-1)                      # the next step's embed launch reads `ids`, not the partials of an earlier step
+        self._steps += n
+        if all_logits:
+            return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+        return self.logits
+
+    @torch.no_grad()
+    def perplexity(self, input_ids):
+        """the reference's evaluation (opt.py:287-297, llama.py:244-250) on the engine's own layers: input_ids int64 [nsamples, seqlen], every
+        sample an independent sequence prefilled from an empty cache (bs samples per pass); shifted cross-entropy in fp32,
+        exp(sum nll / (nsamples * seqlen)) with nll = mean CE of the sample * seqlen.  Returns a float."""
+        input_ids = input_ids.to(self.dev)
+        if input_ids.dim() != 2 or input_ids.shape[1] < 2:
+            raise ValueError("DecodeEngine.perplexity: input_ids must be [nsamples, seqlen >= 2]")
+        nsamples, seqlen = input_ids.shape
+        if seqlen > self.max_len:
+            raise RuntimeError(f"DecodeEngine.perplexity: seqlen {seqlen} > max_len {self.max_len}")
+        nlls = []
+        for lo in range(0, nsamples, self.bs):
+            batch = input_ids[lo:lo + self.bs]
+            real = batch.shape[0]
+            if real < self.bs:                           # the last pass: pad with copies of its first sample, which are not counted
+                batch = torch.cat([batch, batch[:1].expand(self.bs - real, seqlen)])
+            self.reset()
+            lg = self.prefill(batch, all_logits=True)
+            for r in range(real):
+                loss = F.cross_entropy(lg[r, :-1].float(), batch[r, 1:])
+                nlls.append(loss.float() * seqlen)
+        self.reset()
+        return float(torch.exp(torch.stack(nlls).sum() / (nsamples * seqlen)))
+
     @torch.no_grad()
     def generate(self, first, n):
-        """greedy continuation: returns int64 [n, bs] -- the n tokens following `first` (model.generate(do_sample=False) with a cache)"""
-        self.forward(first)
+        """greedy continuation: returns int64 [n, bs] -- the n tokens following `first` (model.generate(do_sample=False) with a cache).
+        `first`: one token per sequence (int or [bs]), or a prompt [bs, n_prompt], which is prefilled in one pass."""
+        if torch.is_tensor(first) and first.dim() == 2 and first.shape[1] > 1:
+            self.prefill(first)
+        else:
+            self.forward(first)
         out = []
         for i in range(n):
             if self._fh:                                 # the embed launch of step i + 1 writes step i's argmax into `ids`
@@ -643,3 +774,21 @@ def benchmark(model, input_ids, check=False, engine=None):
     if check:
         print('PPL:', res["ppl"])
     return res
+
+
+def perplexity(model, testenc, engine=None):
+    """the reference's `opt_eval` / `llama_eval` figure (opt.py:194-297, llama.py:175-251) on the decode engine built over `model` (kept on
+    the model between calls): testenc is the tokenised test set ([1, N] ids, or the tokenizer's output with .input_ids), cut into
+    N // model.seqlen samples of model.seqlen tokens; prints and returns the perplexity"""
+    ids = getattr(testenc, "input_ids", testenc)
+    seqlen = int(model.seqlen)
+    nsamples = ids.numel() // seqlen
+    ids = ids.reshape(-1)[:nsamples * seqlen].reshape(nsamples, seqlen)
+    eng = engine or getattr(model, "_quip_decode_engine", None)
+    if eng is None or eng.max_len < seqlen:
+        eng = DecodeEngine.from_hf(model, max_len=seqlen)
+        model.__dict__["_quip_decode_engine"] = eng
+    print('Evaluating ...')
+    ppl = eng.perplexity(ids)
+    print(ppl)
+    return ppl

@@ -1221,6 +1221,37 @@ def decode_attention_grouped(q, k, v, kcache, vcache, pos, cos_table=None, sin_t
     return out
 
 
+def prefill_attention(q, k, v, kcache, vcache, start, T, cos_table=None, sin_table=None, scale=None):
+    """causal attention over T >= 1 new positions per sequence, two launches (quip_amd/csrc/prefill_attn.hip, include/quip_amd_prefill.h):
+    rows b*T + t of k / v (k rotated when tables are given, exactly as rope_inplace does at position start + t) are appended to the caches
+    at start + t, then out[b*T + t] attends to cache positions 0 .. start + t; query head j reads key / value head j // g (HF's repeat_kv
+    order, g = heads / kv_heads in 1..16).
+    q: [bs*T, heads*hd]; k, v: [bs*T, kv_heads*hd] f16/bf16, row strides multiples of 8, never written; kcache, vcache: [bs, kv_heads,
+    maxlen, hd] contiguous; start: int64 [1] ON THE DEVICE (start < 0 or start + T > maxlen: nothing is written).  Returns out
+    [bs*T, heads*hd].  The result of a row depends on its absolute position only: any cut of a prompt into calls gives the same bits."""
+    _need_gpu(q, k, v, kcache, vcache, start, cos_table, sin_table)
+    bs, kv_heads, maxlen, hd = kcache.shape
+    T = int(T)
+    assert q.dim() == 2 and q.shape[0] == bs * T and q.shape[1] % hd == 0
+    heads = q.shape[1] // hd
+    assert k.shape == (bs * T, kv_heads * hd) and v.shape == k.shape
+    assert kcache.is_contiguous() and vcache.is_contiguous() and vcache.shape == kcache.shape
+    assert start.dtype == torch.int64 and start.numel() == 1
+    assert q.dtype == k.dtype == v.dtype == kcache.dtype == vcache.dtype
+    assert all(t.stride(-1) == 1 for t in (q, k, v))
+    ld = lambda t: t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    rows = 0
+    if cos_table is not None or sin_table is not None:
+        assert cos_table is not None and sin_table is not None and cos_table.dtype == sin_table.dtype == torch.float32
+        assert cos_table.shape == sin_table.shape and cos_table.shape[1] == hd and cos_table.is_contiguous() and sin_table.is_contiguous()
+        rows = cos_table.shape[0]
+    out = torch.empty((bs * T, heads * hd), dtype=q.dtype, device=q.device)
+    sc = float(scale) if scale is not None else 1.0 / (hd ** 0.5)
+    _lib.call("quipamd_prefill_attention", _p(q), _p(k), _p(v), _p(kcache), _p(vcache), _p(start), T, _p(out), _p(cos_table), _p(sin_table),
+              rows, _dtype(q), bs, heads, kv_heads, hd, maxlen, ctypes.c_float(sc), ld(q), ld(k), ld(v), _stream())
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def decode_attention_fused_max_len(hd, p, q):
     """the largest KV-cache maxlen decode_attention_fused serves for head_dim hd with p x q operators (its LDS limit), 0 for a shape it does
