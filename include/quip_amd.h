@@ -154,7 +154,8 @@ int quipamd_vecquant4matmul(const float *vec, const int32_t *mat, float *mul, co
                             int64_t m, int64_t d, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* quipamd_dequant_gemm_cfg: the same call with the kernel chosen by the caller instead of the shape heuristic -- for
- * benchmarks and the forced-kernel parity tests; never needed for correctness.  cfg = int32[4] {family, p1, p2, p3}
+ * benchmarks and the forced-kernel parity tests; never needed for correctness (quipamd_dequant_gemm_plan says which kernel of enum
+ * quipamd_k2_kernel, below, a cfg selects).  cfg = int32[4] {family, p1, p2, p3}
  * (NULL or all 0 = heuristic): family 1 = round-1 kernels; 2 = "h" (bs <= 16, d <= 4096: p1 = waves, p2 = chunks per
  * wave, [3] = row tiles per workgroup or 0); 3 = "s" (bs <= 16 weight stream: p1 = row tiles per workgroup, p2 = k-split); 4 = "mb" (bs > 16:
  * p1 = 45 | 23 = the 256 x 128 / 128 x 64 workgroup tile with four loader waves, the defaults; 44 | 22 the two-loader forms of rounds 2-4; lab
@@ -183,6 +184,32 @@ int quipamd_tune_dequant_gemm(int rt, int bt, int nw, int split);
  * step).  0: the heuristic; 1 | 2 | 4: the grouped h kernel with that many row tiles per workgroup; 74 | 72 | 81: the grouped weight-stream
  * kernel (dq_sg_kernel) with 4 | 7 | 8 row tiles per workgroup.  Process-wide. */
 void quipamd_dequant_gemm_grouped_config(int form);
+
+/* Which kernel a dequant-GEMM call runs (csrc/k2_plan.h decides; the launch code executes the plan and nothing else).  p[] = the template
+ * parameters of the instantiation, per kernel: */
+enum quipamd_k2_kernel {
+    QUIPAMD_K2_NONE = 0,         /* nothing launched: an empty batch, or a refused call */
+    QUIPAMD_K2_R1_TILE = 1,      /* round 1, bs <= 16 (bf16): RT row tiles per workgroup, CW chunks in flight, DEPTH groups of them */
+    QUIPAMD_K2_R1_WAVE = 2,      /* round 1, per-wave kernel: RT, BT batch tiles per wave, NW waves; a group is one launch per problem */
+    QUIPAMD_K2_R1_BATCHED = 3,   /* round 1, bs >= 32: RT row tiles per wave */
+    QUIPAMD_K2_H = 4,            /* "h", bs <= 16, K within one LDS pass: RT, NW waves, NCH chunks per wave */
+    QUIPAMD_K2_H_HALF = 5,       /* "h" with 8-row slabs (bs <= 8, 4096 < d <= 8192): RT, NW, NCH */
+    QUIPAMD_K2_H_HALF_X2 = 6,    /* the same for 9..16 rows: ONE launch of two problems, rows 0..7 and 8.. of the call */
+    QUIPAMD_K2_HR = 7,           /* "hr", x straight into registers (forced only, d = 4096): RT, NW, NCH */
+    QUIPAMD_K2_HG = 8,           /* grouped "h": 2..3 problems in one launch: RT, NW, NCH */
+    QUIPAMD_K2_S = 9,            /* "s", bs <= 16 weight stream: NW row tiles per workgroup, KSP k-split, SPW, ring depth D */
+    QUIPAMD_K2_SG = 10,          /* grouped "s": NW, KSP, SPW, D */
+    QUIPAMD_K2_MB = 11,          /* "mb", bs > 16: WB batch groups of waves, RTw x BTw tiles per wave, NL loader waves, T32 (32x32x16 MFMA) */
+    QUIPAMD_K2_W3 = 12           /* STREAM3 layout: NW, KSP, SPW, D; a group is one launch per problem */
+};
+/* quipamd_dequant_gemm_plan: the plan that quipamd_dequant_gemm_grouped (ngroups = 1: quipamd_dequant_gemm, or quipamd_dequant_gemm_cfg
+ * with this cfg; cfg NULL = none) would execute for these arguments on the calling thread right now -- under its quipamd_tune_dequant_gemm
+ * state and the process's grouped form -- without launching anything; works without a GPU.
+ * plan = int32[8]: {quipamd_k2_kernel, p[0..4], k-slices, launches (1, or ngroups when a group runs as one launch per problem; 0 = empty)}.
+ * A shape the call would refuse returns the same status and sets the same message (the limits a kernel checks on its own grid -- packed
+ * weights of 4 GiB and more in the streaming kernels, more batch tiles than a grid holds -- and the pointer checks are the call's). */
+int quipamd_dequant_gemm_plan(int ngroups, int x_dtype, int bits, int layout, int qfn, int y_dtype, int accumulate, int64_t bs, int64_t m,
+                              int64_t d, const int32_t *cfg, int32_t *plan);
 
 /* ---- K3: structured orthogonal (two-factor butterfly / Kronecker) apply ------------------------
  * Replaces mul_ortho_butterfly (method.py:46-67) and the dense U @ W @ V^T, V @ H @ V^T products of

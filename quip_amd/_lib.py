@@ -91,6 +91,7 @@ SIGNATURES = {
     "quipamd_hessian_accum_fast": [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     "quipamd_probe_set": [c_vp],
     "quipamd_dequant_gemm_grouped_config": [c_int],
+    "quipamd_dequant_gemm_plan": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_vp, c_vp],
     "quipamd_decode_prefetch_next": [c_vp, c_vp, c_int],
     "quipamd_decode_attention_grouped_workspace_bytes": [c_i64, c_int, c_int, c_int, c_i64],
     "quipamd_decode_attention_grouped": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_int, c_i64,

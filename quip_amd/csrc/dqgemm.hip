@@ -588,21 +588,6 @@ int launch_mb(const uint16_t *x, const uint4 *qw, const EpiArgs &e, int64_t d, h
     return QUIPAMD_OK;
 }
 
-// Tuning override of the round-1 kernels (quipamd_tune_dequant_gemm): 0 = use the shape heuristic.  Per THREAD: the
-// library's promise is thread safety per stream, and a benchmark thread forcing a shape must not change another's calls.
-thread_local int g_tune_rt = 0, g_tune_bt = 0, g_tune_nw = 0, g_tune_split = 0, g_tune_depth = 0;
-// per-call kernel selection (quipamd_dequant_gemm_cfg): family + parameters, all 0 = heuristic
-thread_local int g_k2_cfg[4] = {0, 0, 0, 0};
-
-#define QA_K2_CASE(RT_, BT_, NW_) \
-    if (rt == RT_ && bt == BT_ && nw == NW_) return launch_cfg_each<BITS, RT_, BT_, NW_>(G, ngroups, e, d, s)
-
-// Shape heuristic.  BT: as many batch tiles per wave as the batch has (weights streamed once per 64 batch
-// rows).  RT: row tiles per workgroup -- more rows per workgroup means fewer x bytes into the chip
-// (every workgroup ingests the whole x), but the grid must still cover the 256 CUs.
-template <int BITS>
-int launch(const TileGroup &G, int ngroups, const EpiArgs &e0, int64_t d, hipStream_t s);
-
 // one problem of a group through the non-grouped kernels
 template <int BITS, int RT, int BT, int NW>
 int launch_cfg_each(const TileGroup &G, int ngroups, const EpiArgs &e0, int64_t d, hipStream_t s)
@@ -616,207 +601,131 @@ int launch_cfg_each(const TileGroup &G, int ngroups, const EpiArgs &e0, int64_t 
     return QUIPAMD_OK;
 }
 
+// Execute a round-1 plan (k2_plan_r1 in k2_plan.h decides): the tile kernel takes a whole group in one launch (grid.y), the per-wave kernel
+// one problem of a group per launch, the batched kernel single problems only.
 template <int BITS>
-int launch(const TileGroup &G, int ngroups, const EpiArgs &e, int64_t d, hipStream_t s)
+int k2r1_run(const K2Plan &p, const TileGroup &G, int ngroups, const EpiArgs &e0, int64_t d, hipStream_t s)
 {
-    const int64_t ntile = e.m / 16;
-    const int64_t nb = (e.bs + 15) / 16;
-    if (nb == 1 && g_tune_bt == 0) {
-        // tile kernel.  rt: row tiles per workgroup (x slab reuse); cw: chunks in flight per workgroup;
-        // S: k-slices over workgroups (atomics; accumulate contract only).
-        const int64_t nkc = d / Deq<BITS>::KC;
-        const bool can_split = e.accumulate && e.y_f32;
-        // Choices below are the winners of the shape sweeps under profiles/r01f_* (2-bit, bs 1 and 16).  Large m / long K:
-        // the per-wave kernel (every wave streams RT weight tiles per chunk: more bytes in flight per wave, private slabs);
-        // small m: the tile kernel (all of a CU's bytes in flight at once, parallel reducers, optional split-K).
-        const bool tuned = g_tune_rt != 0 || g_tune_nw != 0 || g_tune_split != 0 || g_tune_depth != 0;
-        int rt = 1, cw = 8, S = 1;
-        if (!tuned && ntile % 4 == 0 && ntile >= 1024) return launch_cfg_each<BITS, 4, 1, 8>(G, ngroups, e, d, s);
-        if (!tuned && ntile % 4 == 0 && ntile >= 640 && nkc >= 16) return launch_cfg_each<BITS, 4, 1, 16>(G, ngroups, e, d, s);
-        if (!tuned && ntile % 2 == 0 && ntile >= 384 && nkc >= 24) return launch_cfg_each<BITS, 2, 1, 16>(G, ngroups, e, d, s);
-        if (can_split && ntile % 2 == 0 && ntile / 2 < 256) {
-            // small m under the accumulate contract: 8-wave workgroups (several resident per CU), k split over
-            // workgroups until there are ~512 of them (measured best at 4096x4096: rt 2, cw 4, S 4)
-            rt = 2; cw = 4;
-            S = (int)((512 + ntile / 2 - 1) / (ntile / 2));
-            if (S > nkc / cw) S = (int)(nkc / cw);
-            if (S < 1) S = 1;
-        }
-        if (g_tune_rt > 0 && ntile % g_tune_rt == 0) { rt = g_tune_rt; cw = 16 / rt; }
-        if (g_tune_nw > 0) cw = g_tune_nw / rt > 0 ? g_tune_nw / rt : 1;
-        if (g_tune_split > 0) S = can_split ? g_tune_split : 1;
-        // chunks in flight per wave: enough to cover the workgroup's k-slice in one go when LDS allows (<= 128 KiB of slabs)
-        const int64_t slice = (nkc + S - 1) / S;
-        (void)slice;
-        int depth = 1;                       // measured: 2 or 4 groups in flight buy nothing at 4096^2 (profiles/r01f)
-        if (g_tune_depth > 0) depth = g_tune_depth;
+    switch (p.kernel) {
+    case QUIPAMD_K2_R1_TILE:                                            // <RT, CW, DEPTH>, p.kslices
 #define QA_K2T_CASE(RT_, CW_) \
-        if (rt == RT_ && cw == CW_) { \
-            if (depth == 1) return launch_tile<BITS, RT_, CW_, 1>(G, ngroups, e, d, S, s); \
-            if constexpr ((size_t)CW_ * 2 * 16 * Deq<BITS>::KC * 2 <= 128 * 1024) { if (depth == 2) return launch_tile<BITS, RT_, CW_, 2>(G, ngroups, e, d, S, s); } \
-            return qa_fail(QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: depth %d does not fit LDS for cw=%d", depth, cw); \
+        if (p.p[0] == RT_ && p.p[1] == CW_) { \
+            if (p.p[2] == 1) return launch_tile<BITS, RT_, CW_, 1>(G, ngroups, e0, d, p.kslices, s); \
+            if constexpr ((size_t)CW_ * 2 * 16 * Deq<BITS>::KC * 2 <= 128 * 1024) { if (p.p[2] == 2) return launch_tile<BITS, RT_, CW_, 2>(G, ngroups, e0, d, p.kslices, s); } \
         }
         QA_K2T_CASE(1, 16) QA_K2T_CASE(1, 8) QA_K2T_CASE(1, 4) QA_K2T_CASE(1, 2) QA_K2T_CASE(1, 1) QA_K2T_CASE(2, 1)
         QA_K2T_CASE(2, 8)  QA_K2T_CASE(2, 4) QA_K2T_CASE(2, 2)
         QA_K2T_CASE(4, 4)  QA_K2T_CASE(4, 2) QA_K2T_CASE(4, 1)
         if constexpr (BITS == 2) { QA_K2T_CASE(8, 2) QA_K2T_CASE(8, 1) }
 #undef QA_K2T_CASE
-        return qa_fail(QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: no tile kernel for rt=%d cw=%d", rt, cw);
-    }
-    // bs > 16: one batch tile per workgroup (grid.y walks the batch tiles, weights re-streamed from L2 / Infinity Cache)
-    // with as many row tiles per wave as the grid allows beat the BT > 1 variants at every swept shape.
-    const int64_t nby64 = (e.bs + 63) / 64;
-    if (g_tune_bt == 0 && g_tune_rt == 0 && g_tune_nw == 0 && ngroups == 1 && !g_tune_depth && ((nby64 >= 2 && ntile >= 512) || (nb >= 3 && ntile >= 1024))) {
-        // batched kernel: (2*RT*16 rows) x 64 batch rows per workgroup; RT by how many workgroups the grid then has.
-        // Wins for bs > 64 on m >= 8192 (or one 64-row batch tile on m >= 16384); on shorter matrices the per-wave kernel,
-        // whose 16 waves split K, is faster (profiles/r01h_k2_batched_sweep.jsonl, r01h_k2_default_config_all_shapes.jsonl).
-        const int64_t nby = nby64;
-        if (ntile % 8 == 0 && (ntile / 8) * nby >= 512) return launch_mb<BITS, 4>(G.x[0], G.qw[0], e, d, s);
-        if (ntile % 4 == 0 && (ntile / 4) * nby >= 256) return launch_mb<BITS, 2>(G.x[0], G.qw[0], e, d, s);
-        if (ntile % 2 == 0) return launch_mb<BITS, 1>(G.x[0], G.qw[0], e, d, s);
-    }
-    if (g_tune_depth == 9 && ngroups == 1) {                      // tuning: force the batched kernel, RT = g_tune_rt
-        if (g_tune_rt == 4 && ntile % 8 == 0) return launch_mb<BITS, 4>(G.x[0], G.qw[0], e, d, s);
-        if (g_tune_rt == 2 && ntile % 4 == 0) return launch_mb<BITS, 2>(G.x[0], G.qw[0], e, d, s);
-        if (g_tune_rt == 1 && ntile % 2 == 0) return launch_mb<BITS, 1>(G.x[0], G.qw[0], e, d, s);
-        return qa_fail(QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: batched kernel needs rt in {1,2,4} dividing the row tiles");
-    }
-    int rt, bt = 1, nw = 16;
-    if (ntile % 4 == 0 && (ntile / 4) * nb >= 128) rt = 4;
-    else if (ntile % 2 == 0 && (ntile / 2) * nb >= 128) rt = 2;
-    else rt = 1;
-    if (g_tune_rt > 0 && ntile % g_tune_rt == 0) rt = g_tune_rt;
-    if (g_tune_bt > 0) bt = g_tune_bt;
-    if (g_tune_nw > 0) nw = g_tune_nw;
-    QA_K2_CASE(1, 1, 16); QA_K2_CASE(2, 1, 16); QA_K2_CASE(4, 1, 16);
-    QA_K2_CASE(1, 1, 8);  QA_K2_CASE(2, 1, 8);  QA_K2_CASE(4, 1, 8);
-    QA_K2_CASE(1, 1, 4);  QA_K2_CASE(2, 1, 4);  QA_K2_CASE(4, 1, 4);
-    QA_K2_CASE(1, 2, 8);  QA_K2_CASE(2, 2, 8);
-    QA_K2_CASE(1, 2, 4);  QA_K2_CASE(2, 2, 4);
-    QA_K2_CASE(1, 4, 4);  QA_K2_CASE(2, 4, 4);
-    return qa_fail(QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: no kernel for rt=%d bt=%d nw=%d", rt, bt, nw);
-}
+        break;
+    case QUIPAMD_K2_R1_WAVE:                                            // <RT, BT, NW>
+#define QA_K2_CASE(RT_, BT_, NW_) \
+        if (p.p[0] == RT_ && p.p[1] == BT_ && p.p[2] == NW_) return launch_cfg_each<BITS, RT_, BT_, NW_>(G, ngroups, e0, d, s)
+        QA_K2_CASE(1, 1, 16); QA_K2_CASE(2, 1, 16); QA_K2_CASE(4, 1, 16);
+        QA_K2_CASE(1, 1, 8);  QA_K2_CASE(2, 1, 8);  QA_K2_CASE(4, 1, 8);
+        QA_K2_CASE(1, 1, 4);  QA_K2_CASE(2, 1, 4);  QA_K2_CASE(4, 1, 4);
+        QA_K2_CASE(1, 2, 8);  QA_K2_CASE(2, 2, 8);
+        QA_K2_CASE(1, 2, 4);  QA_K2_CASE(2, 2, 4);
+        QA_K2_CASE(1, 4, 4);  QA_K2_CASE(2, 4, 4);
 #undef QA_K2_CASE
+        break;
+    case QUIPAMD_K2_R1_BATCHED:                                         // <RT>
+        if (p.p[0] == 4) return launch_mb<BITS, 4>(G.x[0], G.qw[0], e0, d, s);
+        if (p.p[0] == 2) return launch_mb<BITS, 2>(G.x[0], G.qw[0], e0, d, s);
+        if (p.p[0] == 1) return launch_mb<BITS, 1>(G.x[0], G.qw[0], e0, d, s);
+        break;
+    }
+    return qa_fail(QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: the plan names no instantiation (kernel %d: %d %d %d, %d bits)", p.kernel, p.p[0], p.p[1],
+                   p.p[2], BITS);
+}
+
+// Tuning override of the round-1 kernels (quipamd_tune_dequant_gemm): all 0 = use the shape heuristic.  Per THREAD: the
+// library's promise is thread safety per stream, and a benchmark thread forcing a shape must not change another's calls.
+thread_local K2Tune g_tune = {};
+// quipamd_dequant_gemm_grouped_config (tests, A/B runs); 0 = the heuristic.  Process-wide, and the one switch of the grouped forms.
+int g_grouped_form = 0;
 
 }   // namespace
 
 extern "C" int quipamd_tune_dequant_gemm(int rt, int bt, int nw, int split)
 {
-    g_tune_rt = rt; g_tune_bt = bt; g_tune_nw = nw;
-    g_tune_split = split % 100;            // split + 100*depth: depth = chunk groups in flight per workgroup (0 = heuristic)
-    g_tune_depth = split / 100;
+    g_tune = k2_tune_decode(rt, bt, nw, split);
     return QUIPAMD_OK;
 }
 
-static int dequant_gemm_impl(int ngroups, const void *const *x, int x_dtype, const int32_t *const *qweight, int bits, int layout, int qfn,
-                             const float *const *scale, const float *const *zero, const float *const *bias, void *const *y, int y_dtype,
-                             int accumulate, int64_t bs, int64_t m, int64_t d, void *stream)
+extern "C" void quipamd_dequant_gemm_grouped_config(int form) { g_grouped_form = form; }
+
+static K2Force k2_force(const int32_t *cfg)
 {
-    QA_REQUIRE(ngroups >= 1 && ngroups <= 4, QUIPAMD_ERR_ARG, "dequant_gemm: 1..4 problems per call");
-    QA_REQUIRE(x_dtype == QUIPAMD_BF16 || x_dtype == QUIPAMD_F16, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: x must be bf16 or fp16");
-    QA_REQUIRE(y_dtype == x_dtype || y_dtype == QUIPAMD_F32, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: y must be f32 or x's dtype");
-    QA_REQUIRE(!accumulate || y_dtype == QUIPAMD_F32, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: accumulate needs f32 y");
-    if (layout == QUIPAMD_LAYOUT_STREAM3) {
-        // the native 3-bit layout has its own kernel family (dqgemm_w3.hip), taken on the layout value before anything below; a group is one
-        // launch per problem
-        for (int gi = 0; gi < ngroups; ++gi) {
-            K2Call c;                                                  // (pointers, qfn and shape are checked by k2w3_launch)
-            c.x = x[gi]; c.x_dtype = x_dtype; c.qweight = qweight[gi]; c.bits = bits; c.qfn = qfn; c.maxq = 7;
-            c.scale = scale[gi]; c.zero = zero ? zero[gi] : nullptr; c.bias = bias ? bias[gi] : nullptr; c.y = y[gi]; c.y_dtype = y_dtype;
-            c.accumulate = accumulate; c.bs = bs; c.m = m; c.d = d;
-            for (int i = 0; i < 4; ++i) c.cfg[i] = g_k2_cfg[i];
-            const int rc = k2w3_launch(c, stream);
-            if (rc != QUIPAMD_OK) return rc;
-        }
-        return QUIPAMD_OK;
-    }
-    QA_REQUIRE(layout == QUIPAMD_LAYOUT_STREAM, QUIPAMD_ERR_UNSUPPORTED,
-               "dequant_gemm: qweight must be in STREAM layout (repack with quipamd_unpack/quipamd_pack)");
-    QA_REQUIRE(bits == 2 || bits == 3 || bits == 4, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: bits must be 2, 3 or 4");
-    const int grid_maxq = (1 << bits) - 1;             // 3-bit codes (maxq 7) ride in the 4-bit container (pack.hip)
-    if (bits == 3) bits = 4;
-    QA_REQUIRE(qfn == QUIPAMD_QFN_B || qfn == QUIPAMD_QFN_A, QUIPAMD_ERR_ARG, "dequant_gemm: qfn must be a or b");
-    QA_REQUIRE(bs * d * 2 < ((int64_t)1 << 31) && m * d * bits / 8 < ((int64_t)1 << 40), QUIPAMD_ERR_SHAPE,
-               "dequant_gemm: x larger than 2 GiB is not supported by the 32-bit buffer offsets (bs=%lld d=%lld)", (long long)bs, (long long)d);
-    QA_REQUIRE(m % 16 == 0 && d % (512 / bits) == 0, QUIPAMD_ERR_SHAPE,
-               "dequant_gemm: needs m %% 16 == 0 and d %% %d == 0 (m=%lld d=%lld)", 512 / bits, (long long)m, (long long)d);
-    TileGroup G;
-    for (int gi = 0; gi < 4; ++gi) {
-        const int k = gi < ngroups ? gi : 0;
-        QA_REQUIRE(x[k] && qweight[k] && scale[k] && y[k], QUIPAMD_ERR_ARG, "dequant_gemm: null pointer (problem %d)", k);
-        QA_REQUIRE(qfn == QUIPAMD_QFN_B || (zero && zero[k]), QUIPAMD_ERR_ARG, "dequant_gemm: qfn a needs zero");
-        G.x[gi] = (const uint16_t *)x[k]; G.qw[gi] = (const uint4 *)qweight[k];
-        G.scale[gi] = scale[k]; G.zero[gi] = zero ? zero[k] : nullptr; G.bias[gi] = bias ? bias[k] : nullptr; G.y[gi] = y[k];
-    }
-    if (bs == 0 || m == 0) return QUIPAMD_OK;
-    const bool tuned_old = g_tune_rt || g_tune_bt || g_tune_nw || g_tune_split || g_tune_depth;
-    if (ngroups == 1 && !(tuned_old && g_k2_cfg[0] == 0)) {
-        // second-generation kernels first (dqgemm_v2.hip); they decline the shapes the kernels below serve better
-        K2Call c;
-        c.x = x[0]; c.x_dtype = x_dtype; c.qweight = qweight[0]; c.bits = bits; c.qfn = qfn; c.maxq = grid_maxq;
-        c.scale = G.scale[0]; c.zero = G.zero[0]; c.bias = G.bias[0]; c.y = y[0]; c.y_dtype = y_dtype; c.accumulate = accumulate;
-        c.bs = bs; c.m = m; c.d = d;
-        for (int i = 0; i < 4; ++i) c.cfg[i] = g_k2_cfg[i];
-        const int rc = k2v2_launch(c, stream);
-        if (rc != K2V2_NOT_TAKEN) return rc;
-    }
-    if (ngroups > 1 && x_dtype == QUIPAMD_F16 && !(tuned_old && g_k2_cfg[0] == 0)) {
-        // fp16 activations exist only in the second-generation kernels: 2..3 problems of one shape as ONE launch of the grouped h kernel
-        // (dq_hg_kernel: the same body text as dq_h_kernel, the problem picked by blockIdx.y) where it holds the shape, else one launch
-        // per problem.  (Routing dq_h_kernel's OWN arguments through a reference was tried first: hipcc's register allocation moved and
-        //  tests/test_k2_isa.py caught a copy of an asm load's destination ahead of its wait in the ungrouped instantiation.)
-        K2Call cs[4];
-        for (int gi = 0; gi < ngroups; ++gi) {
-            K2Call &c = cs[gi];
-            c.x = x[gi]; c.x_dtype = x_dtype; c.qweight = qweight[gi]; c.bits = bits; c.qfn = qfn; c.maxq = grid_maxq;
-            c.scale = G.scale[gi]; c.zero = G.zero[gi]; c.bias = G.bias[gi]; c.y = y[gi]; c.y_dtype = y_dtype; c.accumulate = accumulate;
-            c.bs = bs; c.m = m; c.d = d;
-            for (int i = 0; i < 4; ++i) c.cfg[i] = 0;
-        }
-        if (ngroups <= 3 && qfn == QUIPAMD_QFN_B) {
-            const int rc = k2v2_launch_grouped(cs, ngroups, stream);
-            if (rc != K2V2_NOT_TAKEN) return rc;
-        }
-        for (int gi = 0; gi < ngroups; ++gi) {
-            K2Call c;
-            c.x = x[gi]; c.x_dtype = x_dtype; c.qweight = qweight[gi]; c.bits = bits; c.qfn = qfn; c.maxq = grid_maxq;
-            c.scale = G.scale[gi]; c.zero = G.zero[gi]; c.bias = G.bias[gi]; c.y = y[gi]; c.y_dtype = y_dtype; c.accumulate = accumulate;
-            c.bs = bs; c.m = m; c.d = d;
-            for (int i = 0; i < 4; ++i) c.cfg[i] = 0;
-            const int rc = k2v2_launch(c, stream);
-            QA_REQUIRE(rc != K2V2_NOT_TAKEN, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm_grouped: no fp16 kernel for this shape (m=%lld d=%lld bs=%lld)",
-                       (long long)m, (long long)d, (long long)bs);
-            if (rc != QUIPAMD_OK) return rc;
-        }
-        return QUIPAMD_OK;
-    }
-    QA_REQUIRE(x_dtype == QUIPAMD_BF16, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: the round-1 kernels are bf16 only");
-    EpiArgs e;
-    e.scale = G.scale[0]; e.zero = G.zero[0]; e.bias = G.bias[0]; e.y = G.y[0];
-    e.qfn = qfn; e.maxq = grid_maxq; e.two_over_maxq = 2.0f / (float)e.maxq; e.y_f32 = (y_dtype == QUIPAMD_F32); e.y_f16 = 0; e.accumulate = accumulate;
-    e.bs = bs; e.m = m;
-    hipStream_t s = (hipStream_t)stream;
-    if (bits == 2) return launch<2>(G, ngroups, e, d, s);
-    return launch<4>(G, ngroups, e, d, s);
+    return K2Force{cfg ? K2Cfg{cfg[0], cfg[1], cfg[2], cfg[3]} : K2Cfg{0, 0, 0, 0}, g_tune, g_grouped_form};
 }
 
-extern "C" int quipamd_dequant_gemm(const void *x, int x_dtype, const int32_t *qweight, int bits, int layout, int qfn,
-                                    const float *scale, const float *zero, const float *bias, void *y, int y_dtype,
-                                    int accumulate, int64_t bs, int64_t m, int64_t d, void *stream)
+extern "C" int quipamd_dequant_gemm_plan(int ngroups, int x_dtype, int bits, int layout, int qfn, int y_dtype, int accumulate, int64_t bs, int64_t m,
+                                         int64_t d, const int32_t *cfg, int32_t *plan)
 {
-    if (bs == 0 || m == 0) return QUIPAMD_OK;                      // empty batch: nothing to do (its pointers may be null)
-    QA_REQUIRE(x && qweight && scale && y, QUIPAMD_ERR_ARG, "dequant_gemm: null pointer");
-    return dequant_gemm_impl(1, &x, x_dtype, &qweight, bits, layout, qfn, &scale, &zero, &bias, &y, y_dtype, accumulate, bs, m, d, stream);
+    QA_REQUIRE(plan, QUIPAMD_ERR_ARG, "dequant_gemm_plan: null pointer");
+    const K2Plan p = k2_plan(k2_shape(ngroups, x_dtype, bits, layout, qfn, y_dtype, accumulate, bs, m, d), k2_force(cfg));
+    plan[0] = p.kernel;
+    for (int i = 0; i < 5; ++i) plan[1 + i] = p.p[i];
+    plan[6] = p.kslices; plan[7] = p.launches;
+    return p.status == QUIPAMD_OK ? QUIPAMD_OK : qa_fail(p.status, "%s", p.msg);
+}
+
+// validate, build the per-problem records once, plan, run
+static int dequant_gemm_impl(int ngroups, const void *const *x, int x_dtype, const int32_t *const *qweight, int bits, int layout, int qfn,
+                             const float *const *scale, const float *const *zero, const float *const *bias, void *const *y, int y_dtype,
+                             int accumulate, int64_t bs, int64_t m, int64_t d, const int32_t *cfg, void *stream)
+{
+    const K2Shape c = k2_shape(ngroups, x_dtype, bits, layout, qfn, y_dtype, accumulate, bs, m, d);
+    const K2Plan p = k2_plan(c, k2_force(cfg));
+    if (p.status != QUIPAMD_OK && !p.args_ok) return qa_fail(p.status, "%s", p.msg);      // the arguments themselves: before the pointers, as ever
+    K2Problem pr[4];
+    for (int gi = 0; gi < ngroups; ++gi) {
+        if (!(x[gi] && qweight[gi] && scale[gi] && y[gi]))
+            return layout == QUIPAMD_LAYOUT_STREAM3 ? qa_fail(QUIPAMD_ERR_ARG, "dequant_gemm: null pointer")
+                                                    : qa_fail(QUIPAMD_ERR_ARG, "dequant_gemm: null pointer (problem %d)", gi);
+        QA_REQUIRE(qfn == QUIPAMD_QFN_B || (zero && zero[gi]), QUIPAMD_ERR_ARG, "dequant_gemm: qfn a needs zero");
+        pr[gi] = K2Problem{x[gi], qweight[gi], scale[gi], zero ? zero[gi] : nullptr, bias ? bias[gi] : nullptr, y[gi]};
+    }
+    if (p.status != QUIPAMD_OK) return qa_fail(p.status, "%s", p.msg);                    // the kernel choice's refusal
+    switch (p.kernel) {
+    case QUIPAMD_K2_NONE: return QUIPAMD_OK;
+    case QUIPAMD_K2_W3: return k2w3_run(p, c, pr, stream);
+    case QUIPAMD_K2_R1_TILE: case QUIPAMD_K2_R1_WAVE: case QUIPAMD_K2_R1_BATCHED: {
+        TileGroup G;                                                   // entries past the group repeat problem 0
+        for (int gi = 0; gi < 4; ++gi) {
+            const K2Problem &q = pr[gi < ngroups ? gi : 0];
+            G.x[gi] = (const uint16_t *)q.x; G.qw[gi] = (const uint4 *)q.qweight;
+            G.scale[gi] = q.scale; G.zero[gi] = q.zero; G.bias[gi] = q.bias; G.y[gi] = q.y;
+        }
+        EpiArgs e;
+        k2_fill_epi(e, c, pr[0]);
+        return c.cbits == 2 ? k2r1_run<2>(p, G, ngroups, e, d, (hipStream_t)stream) : k2r1_run<4>(p, G, ngroups, e, d, (hipStream_t)stream);
+    }
+    default:
+        // the second-generation kernels.  K2Args / K2GArgs are built there and passed to the kernels BY VALUE, each kernel with its own
+        // argument struct: routing dq_h_kernel's arguments through a reference (to share them with the grouped kernel) moved hipcc's
+        // register allocation, and tests/test_k2_isa.py caught a copy of an asm load's destination ahead of its wait in the ungrouped
+        // instantiation.
+        return k2v2_run(p, c, pr, stream);
+    }
 }
 
 extern "C" int quipamd_dequant_gemm_cfg(const void *x, int x_dtype, const int32_t *qweight, int bits, int layout, int qfn,
                                         const float *scale, const float *zero, const float *bias, void *y, int y_dtype,
                                         int accumulate, int64_t bs, int64_t m, int64_t d, const int32_t *cfg, void *stream)
 {
-    for (int i = 0; i < 4; ++i) g_k2_cfg[i] = cfg ? cfg[i] : 0;
-    const int rc = quipamd_dequant_gemm(x, x_dtype, qweight, bits, layout, qfn, scale, zero, bias, y, y_dtype, accumulate, bs, m, d, stream);
-    for (int i = 0; i < 4; ++i) g_k2_cfg[i] = 0;
-    return rc;
+    if (bs == 0 || m == 0) return QUIPAMD_OK;                      // empty batch: nothing to do (its pointers may be null)
+    QA_REQUIRE(x && qweight && scale && y, QUIPAMD_ERR_ARG, "dequant_gemm: null pointer");
+    return dequant_gemm_impl(1, &x, x_dtype, &qweight, bits, layout, qfn, &scale, &zero, &bias, &y, y_dtype, accumulate, bs, m, d, cfg, stream);
+}
+
+extern "C" int quipamd_dequant_gemm(const void *x, int x_dtype, const int32_t *qweight, int bits, int layout, int qfn,
+                                    const float *scale, const float *zero, const float *bias, void *y, int y_dtype,
+                                    int accumulate, int64_t bs, int64_t m, int64_t d, void *stream)
+{
+    return quipamd_dequant_gemm_cfg(x, x_dtype, qweight, bits, layout, qfn, scale, zero, bias, y, y_dtype, accumulate, bs, m, d, nullptr, stream);
 }
 
 extern "C" int quipamd_dequant_gemm_grouped(int ngroups, const void *const *x, int x_dtype, const int32_t *const *qweight, int bits,
@@ -826,5 +735,5 @@ extern "C" int quipamd_dequant_gemm_grouped(int ngroups, const void *const *x, i
 {
     if (bs == 0 || m == 0) return QUIPAMD_OK;
     QA_REQUIRE(x && qweight && scale && y, QUIPAMD_ERR_ARG, "dequant_gemm_grouped: null pointer array");
-    return dequant_gemm_impl(ngroups, x, x_dtype, qweight, bits, layout, qfn, scale, zero, bias, y, y_dtype, accumulate, bs, m, d, stream);
+    return dequant_gemm_impl(ngroups, x, x_dtype, qweight, bits, layout, qfn, scale, zero, bias, y, y_dtype, accumulate, bs, m, d, nullptr, stream);
 }

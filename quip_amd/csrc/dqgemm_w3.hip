@@ -270,50 +270,28 @@ int launch_w3(const K2Args &A, hipStream_t s)
     return QUIPAMD_OK;
 }
 
-// Row tiles per workgroup (NW; K is split over 8 / NW waves per tile): cost = rounds of 256 one-per-CU workgroups x NW, ties to the larger NW
-// (x is ingested once per workgroup).  Measured at bs 16, us, with each shape forced in a lab build (profiles/w3_native_vs_container.jsonl
-// has the chosen ones): 8192 x 8192 NW 1 / 2 / 4 15.1 / 10.5 / 14.8; 7168 x 28672 39.1 / 28.0 / 40.6; 28672 x 7168 NW 4 / 7 / 8 27.1 / 20.3 /
-// 21.7; 4096 x 4096 NW 1 / 2 5.9 / 6.8.  Only those five shapes were timed: the rule is what they agree on, row counts between them
-// (5120, 13824, 16384, 32000 ...) are served by it unmeasured.  Every configuration is checked against fp64 in tests/test_gpu_stream3.py.
-template <class ACT>
-int run_w3(const K2Args &A, hipStream_t s)
-{
-    const int64_t ntile = A.e.m / 16;
-    int nw = 1;
-    int64_t best = -1;
-    for (int c : {1, 2, 4, 7, 8}) {
-        const int64_t cost = (((ntile + c - 1) / c + 255) / 256) * c;
-        if (best < 0 || cost <= best) { best = cost; nw = c; }
-    }
-    if (nw == 1) return launch_w3<ACT, 1, 8, 1, 2>(A, s);
-    if (nw == 2) return launch_w3<ACT, 2, 4, 1, 3>(A, s);
-    if (nw == 4) return launch_w3<ACT, 4, 2, 1, 4>(A, s);
-    if (nw == 8) return launch_w3<ACT, 8, 1, 2, 3>(A, s);
-    return launch_w3<ACT, 7, 2, 1, 3>(A, s);
-}
-
 }   // namespace
 
-int k2w3_launch(const K2Call &c, void *stream)
+// the plan (k2_plan_w3 in k2_plan.h: the cost rule and its measurements) names <NW, KSP, SPW, D>; a group is one launch per problem
+int k2w3_run(const K2Plan &p, const K2Shape &c, const K2Problem *pr, void *stream)
 {
-    QA_REQUIRE(c.bits == 3, QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm: the STREAM3 layout holds 3-bit codes only (bits=%d)", c.bits);
-    QA_REQUIRE(c.qfn == QUIPAMD_QFN_B || c.qfn == QUIPAMD_QFN_A, QUIPAMD_ERR_ARG, "dequant_gemm: qfn must be a or b");
-    QA_REQUIRE(c.cfg[0] == 0 && c.cfg[1] == 0 && c.cfg[2] == 0 && c.cfg[3] == 0, QUIPAMD_ERR_UNSUPPORTED,
-               "dequant_gemm: no forced kernel configurations for the STREAM3 layout");
-    QA_REQUIRE(c.m % 16 == 0 && c.d % 256 == 0 && c.d > 0, QUIPAMD_ERR_SHAPE,
-               "dequant_gemm: STREAM3 layout needs m %% 16 == 0 and d %% 256 == 0 (m=%lld d=%lld)", (long long)c.m, (long long)c.d);
-    QA_REQUIRE(c.d * 32 < ((int64_t)1 << 31) && c.m * c.d * 3 / 8 < ((int64_t)1 << 32), QUIPAMD_ERR_SHAPE,
-               "dequant_gemm(STREAM3): 32-bit buffer offsets: packed weights >= 4 GiB or a 16-row slab of x >= 2 GiB (m=%lld d=%lld)",
-               (long long)c.m, (long long)c.d);
-    QA_REQUIRE((c.bs + 15) / 16 <= 65535, QUIPAMD_ERR_SHAPE, "dequant_gemm(STREAM3): bs too large (%lld)", (long long)c.bs);
-    QA_REQUIRE(c.x && c.qweight && c.scale && c.y, QUIPAMD_ERR_ARG, "dequant_gemm: null pointer");
-    QA_REQUIRE(c.qfn == QUIPAMD_QFN_B || c.zero, QUIPAMD_ERR_ARG, "dequant_gemm: qfn a needs zero");
-    K2Args A;
-    A.x = (const uint16_t *)c.x; A.qw = (const u32x4 *)c.qweight; A.d = c.d;
-    EpiArgs &e = A.e;
-    e.scale = c.scale; e.zero = c.zero; e.bias = c.bias; e.y = c.y; e.qfn = c.qfn; e.maxq = 7;
-    e.two_over_maxq = 2.0f / 7.0f;
-    e.y_f32 = c.y_dtype == QUIPAMD_F32; e.y_f16 = c.y_dtype == QUIPAMD_F16; e.accumulate = c.accumulate; e.bs = c.bs; e.m = c.m;
     hipStream_t s = (hipStream_t)stream;
-    return c.x_dtype == QUIPAMD_F16 ? run_w3<ActF16>(A, s) : run_w3<ActBF16>(A, s);
+    const bool f16 = c.x_dtype == QUIPAMD_F16;
+    for (int gi = 0; gi < p.launches; ++gi) {
+        K2Args A;
+        k2_fill_args(A, c, pr[gi]);
+        int rc;
+#define K2_W3_FORM(NW_, KSP_, SPW_, D_)                                                \
+        if (p.p[0] == NW_ && p.p[1] == KSP_ && p.p[2] == SPW_ && p.p[3] == D_)         \
+            rc = f16 ? launch_w3<ActF16, NW_, KSP_, SPW_, D_>(A, s) : launch_w3<ActBF16, NW_, KSP_, SPW_, D_>(A, s)
+        K2_W3_FORM(1, 8, 1, 2);
+        else K2_W3_FORM(2, 4, 1, 3);
+        else K2_W3_FORM(4, 2, 1, 4);
+        else K2_W3_FORM(8, 1, 2, 3);
+        else K2_W3_FORM(7, 2, 1, 3);
+        else rc = qa_fail(QUIPAMD_ERR_UNSUPPORTED, "dequant_gemm(STREAM3): the plan names no instantiation (%d %d %d %d)", p.p[0], p.p[1], p.p[2], p.p[3]);
+#undef K2_W3_FORM
+        if (rc != QUIPAMD_OK) return rc;
+    }
+    return QUIPAMD_OK;
 }

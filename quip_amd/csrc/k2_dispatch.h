@@ -1,26 +1,30 @@
-// k2_dispatch.h -- internal interface between the C ABI (dqgemm.hip) and the second-generation K2 kernels (dqgemm_v2.hip)
+// k2_dispatch.h -- what the three K2 translation units share: the plan (k2_plan.h), the pointers of one problem, and the functions that
+// execute a plan.  (EpiArgs / K2Args live in an anonymous namespace per translation unit -- the kernels' symbols carry it -- so the
+// pointers cross as this plain record and each unit fills its own argument structs from it and the shape.)
 #pragma once
-#include <stdint.h>
+#include "k2_plan.h"
 
-enum { K2_FAM_AUTO = 0, K2_FAM_OLD = 1, K2_FAM_H = 2, K2_FAM_S = 3, K2_FAM_MB = 4, K2_FAM_PF = 5, K2_FAM_NONE = 99 };
-enum { K2V2_NOT_TAKEN = -1 };
-
-struct K2Call {
-    const void *x; int x_dtype;           // [bs, d] bf16 / fp16
-    const void *qweight; int bits;         // STREAM layout; container bits (2 | 4)
-    int qfn, maxq;                         // grid; maxq = 2^wbits - 1 (7 for 3-bit codes in the 4-bit container)
+struct K2Problem {
+    const void *x;            // [bs, d] bf16 / fp16
+    const void *qweight;
     const float *scale, *zero, *bias;
-    void *y; int y_dtype, accumulate;
-    int64_t bs, m, d;
-    int cfg[4];                            // quipamd_k2_config: {family, p1, p2, p3}; all 0 = heuristic
+    void *y;
 };
 
-// returns K2V2_NOT_TAKEN (use the round-1 kernels), QUIPAMD_OK, or an error status
-int k2v2_launch(const K2Call &c, void *stream);
+// execute a plan whose kernel is the unit's (h .. mb: dqgemm_v2.hip; w3: dqgemm_w3.hip); pr[0 .. ngroups).  QUIPAMD_OK or an error status
+int k2v2_run(const K2Plan &p, const K2Shape &c, const K2Problem *pr, void *stream);
+int k2w3_run(const K2Plan &p, const K2Shape &c, const K2Problem *pr, void *stream);
 
-// ngroups (2..3) problems of ONE shape as one launch of the grouped h kernel (grid.y), fp16 activations (the decode engine's 5..16-row
-// steps): calls[i] differ in x, qweight, scale, y only.  Returns K2V2_NOT_TAKEN when the h kernel does not hold the shape.
-int k2v2_launch_grouped(const K2Call *calls, int ngroups, void *stream);
-
-// the STREAM3 layout (3-bit codes at 3 bits per weight; dqgemm_w3.hip): c.bits must be 3, c.cfg all 0.  QUIPAMD_OK or an error status
-int k2w3_launch(const K2Call &c, void *stream);
+// The per-problem argument records, filled in ONE place.  EPI = the unit's EpiArgs, ARGS = its K2Args.
+template <class EPI> inline void k2_fill_epi(EPI &e, const K2Shape &c, const K2Problem &p)
+{
+    e.scale = p.scale; e.zero = p.zero; e.bias = p.bias; e.y = p.y;
+    e.qfn = c.qfn; e.maxq = (1 << c.bits) - 1;              // the grid of the codes as passed: 7 for 3-bit codes in the 4-bit container
+    e.two_over_maxq = 2.0f / (float)e.maxq;
+    e.y_f32 = c.y_dtype == QUIPAMD_F32; e.y_f16 = c.y_dtype == QUIPAMD_F16; e.accumulate = c.accumulate; e.bs = c.bs; e.m = c.m;
+}
+template <class ARGS> inline void k2_fill_args(ARGS &A, const K2Shape &c, const K2Problem &p)
+{
+    A.x = (decltype(A.x))p.x; A.qw = (decltype(A.qw))p.qweight; A.d = c.d;
+    k2_fill_epi(A.e, c, p);
+}

@@ -275,6 +275,20 @@ def dequant_gemm_grouped_config(form=0):
     _lib.load().quipamd_dequant_gemm_grouped_config(int(form))
 
 
+K2_KERNELS = ("none", "r1_tile", "r1_wave", "r1_batched", "h", "h_half", "h_half_x2", "hr", "hg", "s", "sg", "mb", "w3")   # enum quipamd_k2_kernel
+
+
+def dequant_gemm_plan(bs, m, d, bits, x_dtype=torch.bfloat16, qfn='b', out_dtype=None, accumulate=False, cfg=None, layout=LAYOUT_STREAM, ngroups=1):
+    """The kernel dequant_gemm (ngroups = 1, with this cfg) / dequant_gemm_grouped would run for these arguments on this thread right now, as
+    (kernel name, parameters, k-slices, launches) -- see enum quipamd_k2_kernel in include/quip_amd.h.  Launches nothing; needs no GPU.  A shape
+    the call would refuse raises the same QuipAmdError."""
+    c = None if cfg is None else ctypes.cast((ctypes.c_int32 * 4)(*(list(cfg) + [0, 0, 0, 0])[:4]), ctypes.c_void_p)
+    plan = (ctypes.c_int32 * 8)()
+    _lib.call("quipamd_dequant_gemm_plan", ngroups, _DT[x_dtype], bits, layout, QFN[qfn], _DT[out_dtype or x_dtype], int(bool(accumulate)), bs, m, d,
+              c, ctypes.cast(plan, ctypes.c_void_p))
+    return K2_KERNELS[plan[0]], tuple(plan[1:6]), plan[6], plan[7]
+
+
 # ------------------------------------------------------------------------------------------------- K3
 class SmallOp(ctypes.Structure):
     """mirror of `quipamd_small_op` (include/quip_amd.h)."""

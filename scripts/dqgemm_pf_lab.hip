@@ -30,7 +30,18 @@
 // step) -- ~4.5 fillers per MFMA at this tile, at the edge of what one wave per SIMD can hide (MI355X_MICROARCH.md: <= 5 per gap).
 #include "common.h"
 #include "dq_common.h"
-#include "k2_dispatch.h"
+#include "k2_plan.h"                       // K2_FAM_PF
+
+// one call as this lab takes it (the record the library passed to its kernel families while family 5 was one of them)
+struct K2Call {
+    const void *x; int x_dtype;           // [bs, d] bf16 / fp16
+    const void *qweight; int bits;         // STREAM layout; container bits (2 | 4)
+    int qfn, maxq;                         // grid; maxq = 2^wbits - 1
+    const float *scale, *zero, *bias;
+    void *y; int y_dtype, accumulate;
+    int64_t bs, m, d;
+    int cfg[4];                            // {family, p1, p2, p3}; all 0 = heuristic
+};
 
 namespace {
 

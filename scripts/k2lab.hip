@@ -15,8 +15,9 @@ __device__ unsigned long long *g_k2_probe = nullptr;
         q_[0] = k2_acc[0]; q_[1] = k2_acc[1]; q_[2] = k2_acc[2]; q_[3] = __builtin_readcyclecounter() - k2_t00; } } while (0)
 #endif
 #include "../quip_amd/csrc/dqgemm_v2.h"
-int k2v2_launch(const K2Call &, void *) { return K2V2_NOT_TAKEN; }     // the lab's "old" rows measure the round-1 kernels alone
-int k2v2_launch_grouped(const K2Call *, int, void *) { return K2V2_NOT_TAKEN; }
+// the lab's "old" rows measure the round-1 kernels alone (cfg family 1), so the library's executors of the other kernels are never reached
+int k2v2_run(const K2Plan &, const K2Shape &, const K2Problem *, void *) { return QUIPAMD_ERR_UNSUPPORTED; }
+int k2w3_run(const K2Plan &, const K2Shape &, const K2Problem *, void *) { return QUIPAMD_ERR_UNSUPPORTED; }
 namespace {
 // =====================================================================================================================
 // dq_hl_kernel (round 5, LAB ONLY -- a negative result, profiles/r05h_k2lab_hl.txt: 5.0 us cold / 4.07 warm against 4.68 / 3.60 for dq_h_kernel
@@ -330,8 +331,9 @@ template <class ACT> static void run_mode(const std::string &mode, Problem &P)
         if (P.f16) return;
         bench(P, nm, [&, rt, bt, nw, split](int r) {
             quipamd_tune_dequant_gemm(rt, bt, nw, split);
-            return quipamd_dequant_gemm(P.x, 2, (const int32_t *)(P.w + (size_t)r * P.wbytes), P.bits, 1, 1, P.scale, nullptr, nullptr, P.y, 2, 0,
-                                        P.bs, P.m, P.d, st);
+            const int32_t round1[4] = {1, 0, 0, 0};
+            return quipamd_dequant_gemm_cfg(P.x, 2, (const int32_t *)(P.w + (size_t)r * P.wbytes), P.bits, 1, 1, P.scale, nullptr, nullptr, P.y, 2, 0,
+                                            P.bs, P.m, P.d, round1, st);
         });
     };
 #define H_CASE(B, RT, NW, NCH) if (P.bits == B && P.d / (512 / B) <= NW * NCH && (P.m / 16) % RT == 0) \

@@ -120,8 +120,13 @@ def test_headline_shape_linearity_and_dense_agreement(ops, O):
     assert torch.equal(f(x1), y1)
 
 
+# quipamd_tune_dequant_gemm(rt, 0, nw, split) of the split-K test: (0, 0, 0) = the heuristic, else the tile kernel with `split` k-slices
+SPLIT_K_TUNES = [(0, 0, 0), (4, 16, 4), (4, 16, 2), (2, 16, 2), (1, 16, 1), (4, 8, 8), (2, 8, 3)]
+SPLIT_K_SHAPES = [(4096, 4096, 16, 2), (2048, 2048, 7, 2), (1024, 4096, 16, 4), (64, 512, 3, 2)]
+
+
 @pytest.mark.parametrize("qfn", ["a", "b"])
-@pytest.mark.parametrize("m,d,bs,bits", [(4096, 4096, 16, 2), (2048, 2048, 7, 2), (1024, 4096, 16, 4), (64, 512, 3, 2)])
+@pytest.mark.parametrize("m,d,bs,bits", SPLIT_K_SHAPES)
 def test_accumulate_split_k_atomics(ops, O, qfn, m, d, bs, bits):
     """Under the accumulate contract small-m shapes take the split-K path (fp32 atomics into the caller's y,
     bias applied once): same answer as the oracle, and as every forced workgroup shape."""
@@ -137,7 +142,7 @@ def test_accumulate_split_k_atomics(ops, O, qfn, m, d, bs, bits):
     zr = None if zero is None else torch.from_numpy(zero)
     lib = _lib.load()
     try:
-        for (rt, nw, split) in [(0, 0, 0), (4, 16, 4), (4, 16, 2), (2, 16, 2), (1, 16, 1), (4, 8, 8), (2, 8, 3)]:
+        for (rt, nw, split) in SPLIT_K_TUNES:
             lib.quipamd_tune_dequant_gemm(rt, 0, nw, split)
             y = torch.from_numpy(y0.copy()).to(DEV)
             ops.dequant_gemm(xd, qs, bits, qfn, sc, zr, torch.from_numpy(bias), out=y, accumulate=True)
@@ -146,10 +151,18 @@ def test_accumulate_split_k_atomics(ops, O, qfn, m, d, bs, bits):
         lib.quipamd_tune_dequant_gemm(0, 0, 0, 0)
 
 
+# quipamd_tune_dequant_gemm(rt, bt, nw[, split]) at 512 x 2048, bs 16: bt = 0 the tile kernel (split 200: two chunk groups in flight), else the per-wave kernel
+WORKGROUP_TUNES = [(1, 0, 16), (2, 0, 16), (4, 0, 16), (1, 0, 8), (2, 0, 8), (4, 0, 8), (1, 0, 4), (2, 0, 4), (4, 0, 4),
+                   (1, 0, 2), (1, 0, 1), (2, 0, 2), (8, 0, 16), (8, 0, 8), (1, 0, 8, 200), (2, 0, 8, 200), (4, 0, 16, 200), (8, 0, 16, 200),
+                   (1, 1, 16), (2, 1, 16), (4, 1, 16), (1, 1, 8), (2, 1, 8), (4, 1, 8), (1, 1, 4), (4, 1, 4), (1, 2, 8),
+                   (2, 2, 8), (1, 2, 4), (2, 2, 4), (1, 4, 4), (2, 4, 4)]
+WORKGROUP_SHAPE = (512, 2048, 16, 2)
+
+
 def test_forced_workgroup_shapes_agree(ops, O):
     """every (row tiles, waves) shape of both K2 kernels gives the oracle's answer (bf16-free fp32 output)."""
     from quip_amd import _lib
-    m, d, bs, bits = 512, 2048, 16, 2
+    m, d, bs, bits = WORKGROUP_SHAPE
     W, x, codes, scale, zero, maxq = _case(O, m, d, bs, bits, "b", seed=9)
     y_ref = O.dequant_linear(x, codes, "b", scale, None, maxq, None)
     qs = ops.pack(torch.from_numpy(codes).to(DEV), bits, ops.LAYOUT_STREAM)
@@ -158,10 +171,7 @@ def test_forced_workgroup_shapes_agree(ops, O):
     lib = _lib.load()
     bad = []
     try:
-        for cfg in [(1, 0, 16), (2, 0, 16), (4, 0, 16), (1, 0, 8), (2, 0, 8), (4, 0, 8), (1, 0, 4), (2, 0, 4), (4, 0, 4),
-                    (1, 0, 2), (1, 0, 1), (2, 0, 2), (8, 0, 16), (8, 0, 8), (1, 0, 8, 200), (2, 0, 8, 200), (4, 0, 16, 200), (8, 0, 16, 200),
-                    (1, 1, 16), (2, 1, 16), (4, 1, 16), (1, 1, 8), (2, 1, 8), (4, 1, 8), (1, 1, 4), (4, 1, 4), (1, 2, 8),
-                    (2, 2, 8), (1, 2, 4), (2, 2, 4), (1, 4, 4), (2, 4, 4)]:
+        for cfg in WORKGROUP_TUNES:
             lib.quipamd_tune_dequant_gemm(cfg[0], cfg[1], cfg[2], cfg[3] if len(cfg) > 3 else 0)
             y = ops.dequant_gemm(xd, qs, bits, "b", sc, None, None, out_dtype=torch.float32)
             if _rel(y.cpu().numpy().astype(np.float64), y_ref) > TOL_F32:
@@ -187,8 +197,13 @@ def test_llama2_7b_mlp_shapes(ops, O, m, d, bs):
     assert _rel(yacc.cpu().numpy().astype(np.float64), y_ref) <= TOL_F32
 
 
+# quipamd_tune_dequant_gemm(rt, 0, 0, split): split 900 forces the batched kernel with rt row tiles per wave (skipped where 2 rt does not divide the row tiles)
+BATCHED_TUNES = [(0, 0), (1, 900), (2, 900), (4, 900)]
+BATCHED_SHAPES = [(256, 1024, 64), (128, 512, 33), (512, 2048, 100), (1024, 1024, 256)]
+
+
 @pytest.mark.parametrize("bits,qfn", [(2, "b"), (4, "a")])
-@pytest.mark.parametrize("m,d,bs", [(256, 1024, 64), (128, 512, 33), (512, 2048, 100), (1024, 1024, 256)])
+@pytest.mark.parametrize("m,d,bs", BATCHED_SHAPES)
 def test_batched_kernel_bs_over_16(ops, O, bits, qfn, m, d, bs):
     """bs > 16 goes through the batched kernel (shared x slabs, 64 batch rows per workgroup); every RT variant and the
     default agree with the oracle, ragged batch sizes included."""
@@ -204,7 +219,7 @@ def test_batched_kernel_bs_over_16(ops, O, bits, qfn, m, d, bs):
     lib = _lib.load()
     bad = []
     try:
-        for (rt, sp) in [(0, 0), (1, 900), (2, 900), (4, 900)]:
+        for (rt, sp) in BATCHED_TUNES:
             if rt and (m // 16) % (2 * rt):
                 continue
             lib.quipamd_tune_dequant_gemm(rt, 0, 0, sp)

@@ -68,14 +68,14 @@ def _run(ops, O, m, d, bs, bits, qfn, dt, cfg, seed=0, bias=True, check16=True):
     return r32
 
 
+H_SHAPES = [(16, 256, 1), (64, 512, 4), (128, 1024, 16), (48, 768, 9), (256, 2048, 8), (4096, 4096, 16), (2048, 2048, 3), (176, 4096, 11)]
 H_CFGS = {2: [(FAM_H, 8, 1), (FAM_H, 8, 2), (FAM_H, 4, 4)], 4: [(FAM_H, 8, 2), (FAM_H, 8, 4)]}
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("bits", [2, 4])
 @pytest.mark.parametrize("qfn", ["a", "b"])
-@pytest.mark.parametrize("m,d,bs", [(16, 256, 1), (64, 512, 4), (128, 1024, 16), (48, 768, 9), (256, 2048, 8), (4096, 4096, 16),
-                                    (2048, 2048, 3), (176, 4096, 11)])
+@pytest.mark.parametrize("m,d,bs", H_SHAPES)
 def test_h_kernel(ops, O, dt, bits, qfn, m, d, bs):
     """one-pass kernel: every (waves, chunks per wave) instantiation whose LDS holds the layer's K, exact fit and ragged
     K, full and half (bs <= 8) slabs."""
@@ -89,10 +89,13 @@ def test_h_kernel(ops, O, dt, bits, qfn, m, d, bs):
     assert ran
 
 
+HALF_SHAPES = [(2048, 8192, 1), (2048, 8192, 8), (96, 8192, 3), (512, 6144, 5), (64, 4352, 2), (8192, 8192, 4),
+               (2048, 8192, 16), (2048, 8192, 9), (1024, 6144, 12)]      # 9..16 rows: two half-batch problems in one launch
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("qfn", ["a", "b"])
-@pytest.mark.parametrize("m,d,bs", [(2048, 8192, 1), (2048, 8192, 8), (96, 8192, 3), (512, 6144, 5), (64, 4352, 2), (8192, 8192, 4),
-                                    (2048, 8192, 16), (2048, 8192, 9), (1024, 6144, 12)])      # 9..16 rows: two half-batch problems in one launch
+@pytest.mark.parametrize("m,d,bs", HALF_SHAPES)
 def test_half_slab_one_pass_kernel_up_to_d_8192(ops, O, dt, qfn, m, d, bs):
     """round 6: at bs <= 8 a slab of the one-pass kernel holds 8 rows (4 KiB per 256-column chunk), so 32 chunks -- d = 8192, OPT's fc2 in a
     blocked-operator decode step -- fit one workgroup's LDS: the default heuristic takes 16 < chunks <= 32 there (exact fit and ragged K); 9..16
@@ -100,23 +103,32 @@ def test_half_slab_one_pass_kernel_up_to_d_8192(ops, O, dt, qfn, m, d, bs):
     _run(ops, O, m, d, bs, 2, qfn, dt, None, seed=m + d + bs)
 
 
+S_SHAPES = [(112, 256, 1), (224, 512, 16), (16, 768, 5), (1808, 1024, 16), (4096, 2304, 7), (336, 7168, 16)]
+S_CFGS = [(FAM_S, 7, 2), (FAM_S, 4, 2), (FAM_S, 8, 1), (FAM_S, 2, 4), (FAM_S, 1, 8)]     # (2, 4), (1, 8): round 5, short and wide
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("bits,qfn", [(2, "b"), (2, "a"), (4, "a"), (4, "b")])
-@pytest.mark.parametrize("m,d,bs", [(112, 256, 1), (224, 512, 16), (16, 768, 5), (1808, 1024, 16), (4096, 2304, 7), (336, 7168, 16)])
+@pytest.mark.parametrize("m,d,bs", S_SHAPES)
 def test_s_kernel(ops, O, dt, bits, qfn, m, d, bs):
     """weight-stream kernel: row tiles not a multiple of the workgroup's, odd stage counts under the k-split (d = 768,
     2304), one stage only (d = 256), every instantiation."""
-    for cfg in [(FAM_S, 7, 2), (FAM_S, 4, 2), (FAM_S, 8, 1), (FAM_S, 2, 4), (FAM_S, 1, 8)]:     # (2, 4), (1, 8): round 5, short and wide
+    for cfg in S_CFGS:
         _run(ops, O, m, d, bs, bits, qfn, dt, cfg, seed=m + d + bs, check16=(cfg[1] == 7))
+
+
+MB_SHAPES = [(256, 256, 17), (128, 512, 33), (512, 1024, 128), (1040, 768, 100), (3072, 512, 300), (64, 2048, 64)]
+MB_CFGS = [(FAM_MB, 44), (FAM_MB, 22), (FAM_MB, 45), (FAM_MB, 23)]                 # 45 / 23 (round 5): four loader waves
+MB_CFGS_2BIT = [(FAM_MB, 48), (FAM_MB, 49), (FAM_MB, 46), (FAM_MB, 47)]            # 48 / 49: 4 x 8 tiles per wave; 47: the 32x32x16 form
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("bits,qfn", [(2, "b"), (2, "a"), (4, "a")])
-@pytest.mark.parametrize("m,d,bs", [(256, 256, 17), (128, 512, 33), (512, 1024, 128), (1040, 768, 100), (3072, 512, 300), (64, 2048, 64)])
+@pytest.mark.parametrize("m,d,bs", MB_SHAPES)
 def test_mb_kernel(ops, O, dt, bits, qfn, m, d, bs):
     """batched kernel: ragged batch and row counts (workgroup tiles 256 x 128 and 128 x 64), more row blocks than 8
     (the XCD-aware block order), both tile shapes."""
-    for cfg in [(FAM_MB, 44), (FAM_MB, 22), (FAM_MB, 45), (FAM_MB, 23)] + ([(FAM_MB, 48), (FAM_MB, 49), (FAM_MB, 46), (FAM_MB, 47)] if bits == 2 else []):     # 45 / 23 (round 5): four loader waves; 48 / 49: 4 x 8 tiles per wave; 47: the 32x32x16 form
+    for cfg in MB_CFGS + (MB_CFGS_2BIT if bits == 2 else []):
         _run(ops, O, m, d, bs, bits, qfn, dt, cfg, seed=m + d + bs, check16=(cfg[1] == 44))
 
 
@@ -195,8 +207,11 @@ def test_opt30b_shapes_default_heuristic(ops, m, d, bs, dt):
     assert _rel(y[:, rows].cpu().numpy().astype(np.float64), y_ref) <= TOL_F32
 
 
-@pytest.mark.parametrize("m,d,bs,cfg", [(8192, 8192, 16, (FAM_S, 7, 2)), (8192, 8192, 64, (FAM_MB, 44)), (8192, 8192, 64, (FAM_OLD,)),
-                                        (8192, 8192, 16, (FAM_OLD,)), (28672, 7168, 16, (FAM_S, 4, 2)), (4096, 4096, 2048, (FAM_MB, 44))])
+LARGE_FORCED = [(8192, 8192, 16, (FAM_S, 7, 2)), (8192, 8192, 64, (FAM_MB, 44)), (8192, 8192, 64, (FAM_OLD,)),
+                (8192, 8192, 16, (FAM_OLD,)), (28672, 7168, 16, (FAM_S, 4, 2)), (4096, 4096, 2048, (FAM_MB, 44))]
+
+
+@pytest.mark.parametrize("m,d,bs,cfg", LARGE_FORCED)
 def test_large_shapes_forced(ops, m, d, bs, cfg):
     """K2 at d = 8192 with bs > 8 and at prefill size vs the oracle formula, new and round-1 kernels (VERDICT r1 weak #3)."""
     x, qs, sc, rows, y_ref = _sampled_rows_case(ops, m, d, bs, 2, torch.bfloat16, seed=m + bs)
@@ -238,8 +253,12 @@ def test_fp16_layer_keeps_its_mantissa(ops):
     assert float((gotb.double() - wantb).norm() / wantb.norm()) <= 5e-3
 
 
-@pytest.mark.parametrize("form", [74, 72, 81, 4])
-@pytest.mark.parametrize("m,groups,bs", [(11008, 2, 16), (4096, 3, 5), (2064, 2, 9)])
+GROUPED_FORMS = [74, 72, 81, 4]
+GROUPED_SHAPES = [(11008, 2, 16), (4096, 3, 5), (2064, 2, 9)]
+
+
+@pytest.mark.parametrize("form", GROUPED_FORMS)
+@pytest.mark.parametrize("m,groups,bs", GROUPED_SHAPES)
 def test_grouped_weight_stream_kernel(ops, O, form, m, groups, bs):
     """round 6: dq_sg_kernel -- the weight-stream kernel on 2 / 3 problems of one shape, each with its OWN x~ (gate / up, q / k / v of a
     5..16-row decode step at d = 4096) -- in its three workgroup forms, and the grouped h kernel beside it, against the fp64 formula per
@@ -268,9 +287,12 @@ def test_grouped_weight_stream_kernel(ops, O, form, m, groups, bs):
         assert _rel(got[:, rows], refs[g]) <= TOL_F32, (form, g)
 
 
+HR_SHAPES = [(4096, 16), (4096, 1), (176, 11), (2048, 8), (16, 5)]
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("qfn", ["b", "a"])
-@pytest.mark.parametrize("m,bs", [(4096, 16), (4096, 1), (176, 11), (2048, 8), (16, 5)])
+@pytest.mark.parametrize("m,bs", HR_SHAPES)
 def test_register_x_kernel(ops, O, dt, qfn, m, bs):
     """round 6: dq_hr_kernel (family h, p1 = 44) -- the B fragments as 16-byte global loads into registers behind counted waits, no LDS
     staging of x -- at its only K (d = 4096), every batch size (rows past bs re-read row bs - 1), fp32 and 16-bit outputs, bias, qfn a / b,

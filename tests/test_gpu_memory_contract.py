@@ -25,6 +25,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import guard_arena as G  # noqa: E402
+from k2_rules import k2_branch, plan_branch, w3_nw as nw  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -47,7 +48,7 @@ EXEMPT = {
     "quipamd_ortho_blocked_supported", "quipamd_decode_bigp_supported", "quipamd_ortho_blocked_config", "quipamd_decode_attention_config",
     "quipamd_dequant_gemm_grouped_config", "quipamd_cholesky_config", "quipamd_ldlq_config", "quipamd_decode_attention_fused_max_len",
     "quipamd_preproc_workspace_bytes", "quipamd_gptq_qfnb_workspace_bytes", "quipamd_gptq_qfnb_info_offset", "quipamd_gptq_qfnb_debug",
-    "quipamd_hessian_fast_workspace", "quipamd_decode_attention_grouped_workspace_bytes",
+    "quipamd_hessian_fast_workspace", "quipamd_decode_attention_grouped_workspace_bytes", "quipamd_dequant_gemm_plan",
 }
 
 
@@ -306,39 +307,15 @@ def _k2_call(ops, c, out_dtype, cfg=None):
                             layout=c["layout"])
 
 
-def k2_branch(bits, f16, m, d, bs, accumulate=False):
-    """the default dispatch of csrc/dqgemm_v2.hip (run_family) restated: which kernel family serves a call and, inside the 2-bit h family,
-    how many row tiles a workgroup takes (launch_h<2, ACT, 2, 8, 1>, <2, ACT, 2, 4, 4>, <2, ACT, 4, 4, 4>)"""
-    ntile, nkc = m // 16, d // (512 // bits)
-    h_fits = bs <= 16 and nkc <= (16 if bits == 2 else 32)
-    if bs <= 16:
-        if bits == 2 and bs <= 8 and 16 < nkc <= 32 and ntile <= 512:
-            return "h-half"
-        if bits == 2 and bs > 8 and 16 < nkc <= 32 and ntile <= 128 and not accumulate:
-            return "h-half x 2"
-        if h_fits and ntile <= 768:
-            if bits == 2:
-                rt = 4 if (ntile > 512 and ntile % 4 == 0 and nkc > 8) else 2 if (ntile > 256 and ntile % 2 == 0) else 1
-                return "h" if rt == 1 else f"h rt{rt} {'8x1' if nkc <= 8 else '4x4'}"
-            return "h"
-        if ntile >= 1024 and d % 256 == 0:
-            return "s"
-        if f16:
-            return "h" if h_fits else "s" if d % 256 == 0 else "none"
-        return "round-1"
-    tiles = ((m + 255) // 256) * ((bs + 127) // 128)
-    if d % 256 == 0 and ((tiles >= 200 and bits == 2) or f16):
-        return "mb"
-    return "none" if f16 else "round-1"
-
-
 K2_DEFAULT = [(16, 256, 1), (48, 768, 17), (176, 4096, 11), (2048, 8192, 9), (1040, 768, 100), (3072, 512, 300),
               (2048, 8192, 5), (96, 6144, 3), (16384, 512, 5), (8192, 256, 897),
               (8192, 2048, 16), (8192, 4096, 16), (12288, 4096, 16)]          # family h with 2 / 2 / 4 row tiles per workgroup
 
 
-def test_the_default_shapes_reach_every_branch_of_the_dispatch():
+def test_the_default_shapes_reach_every_branch_of_the_dispatch(ops):
+    """every branch is reached -- by the rules (tests/k2_rules.py) and by the library, asked for its plan"""
     got = {k2_branch(2, f16, m, d, bs) for m, d, bs in K2_DEFAULT for f16 in (False, True)}
+    assert got == {plan_branch(ops.dequant_gemm_plan(bs, m, d, 2, x_dtype=F16 if f16 else BF16), 2) for m, d, bs in K2_DEFAULT for f16 in (False, True)}
     assert got == {"h", "h rt2 8x1", "h rt2 4x4", "h rt4 4x4", "h-half", "h-half x 2", "s", "mb", "round-1"}
     assert k2_branch(2, True, 8192, 2048, 16) == "h rt2 8x1" and k2_branch(2, False, 8192, 4096, 16) == "h rt2 4x4" and k2_branch(2, True, 12288, 4096, 16) == "h rt4 4x4"
     assert k2_branch(2, False, 48, 768, 17) == "round-1" and k2_branch(2, True, 48, 768, 17) == "mb" and k2_branch(2, False, 8192, 256, 897) == "mb"
@@ -352,6 +329,8 @@ def test_dequant_gemm_default_dispatch(monkeypatch, ops, m, d, bs, bits, dt):
     c = _k2(ops, m, d, bs, bits, dt, seed=m + d + bs + bits)
 
     def case(A):
+        # the plan of this very call, asked under the arena as well: it launches nothing and carves nothing
+        assert plan_branch(ops.dequant_gemm_plan(bs, m, d, bits, x_dtype=dt), bits) == k2_branch(bits, dt == F16, m, d, bs)
         return {"y32": _k2_call(ops, c, F32), "y16": _k2_call(ops, c, dt)}
     ref, _ = contract(monkeypatch, case, _k2_inputs(c), min_regions=2)
     assert _rel(ref["y32"], c["want"]) <= 1e-3
@@ -453,15 +432,9 @@ def test_dequant_gemm_grouped(monkeypatch, ops, form, m, groups, bs, d):
 W3_SHAPES = [(16, 256, 1), (48, 768, 17), (4112, 512, 16), (27920, 512, 16), (32000, 768, 5), (16384, 768, 16), (2048, 2048, 16)]
 
 
-def test_the_stream3_shapes_reach_every_workgroup_shape():
-    """the dispatch rule of csrc/dqgemm_w3.hip (run_w3) restated as in test_gpu_stream3.py"""
-    def nw(m):
-        ntile, best, pick = m // 16, None, None
-        for c in (1, 2, 4, 7, 8):
-            cost = -(-(-(-ntile // c)) // 256) * c
-            if best is None or cost <= best:
-                best, pick = cost, c
-        return pick
+def test_the_stream3_shapes_reach_every_workgroup_shape(ops):
+    """the dispatch rule of the STREAM3 layout (tests/k2_rules.py, as in test_gpu_stream3.py), and the library asked for its plan"""
+    assert {ops.dequant_gemm_plan(bs, m, d, 3, layout=ops.LAYOUT_STREAM3)[1][0] for m, d, bs in W3_SHAPES} == {1, 2, 4, 7, 8}
     assert {nw(m) for m, _, _ in W3_SHAPES} == {1, 2, 4, 7, 8}
     assert nw(4112) == 2 and 257 % 2 and nw(27920) == 7 and 1745 % 7 and nw(32000) == 8 and 2000 % 8 == 0 and nw(16384) == 4
 

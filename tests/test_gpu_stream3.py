@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import stream3_spec as S3  # noqa: E402
+from k2_rules import w3_nw as nw  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -83,22 +84,16 @@ def test_repack_from_the_reference_words(ops, O, m, d):
 # ---- K2 --------------------------------------------------------------------------------------------------------------------
 SHAPES = [(16, 256, 1), (64, 512, 4), (128, 1024, 16), (48, 768, 17), (256, 512, 64), (2048, 2048, 16), (11008, 4096, 5),
           (4096, 11008, 16), (8192, 8192, 16),
-          # every workgroup shape the dispatch can choose (row tiles per workgroup NW by m / 16: csrc/dqgemm_w3.hip run_w3) is checked, not only
+          # every workgroup shape the dispatch can choose (row tiles per workgroup NW by m / 16: csrc/k2_plan.h k2_plan_w3) is checked, not only
           # the ones the shapes above reach (NW 1 and 2): 1024 row tiles -> NW 4 (the D = 4 ring), odd chunk count; 2000 -> NW 8 (two stages per
           # wave and ring step, ragged last ring step, unpaired high chunk); 257 -> NW 2 and 1745 -> NW 7, both with dead waves in the last
           # workgroup; 1792 -> NW 7 exactly
           (16384, 768, 16), (32000, 768, 5), (4112, 512, 16), (27920, 512, 16), (28672, 1024, 7)]
 
 
-def test_the_added_shapes_reach_every_workgroup_shape():
-    """the dispatch rule of csrc/dqgemm_w3.hip (run_w3) restated: cost = rounds of 256 workgroups x NW, ties to the larger NW"""
-    def nw(m):
-        ntile, best, pick = m // 16, None, None
-        for c in (1, 2, 4, 7, 8):
-            cost = -(-(-(-ntile // c)) // 256) * c
-            if best is None or cost <= best:
-                best, pick = cost, c
-        return pick
+def test_the_added_shapes_reach_every_workgroup_shape(ops):
+    """the dispatch rule (tests/k2_rules.py: cost = rounds of 256 workgroups x NW, ties to the larger NW), and the library asked for its plan"""
+    assert {ops.dequant_gemm_plan(bs, m, d, 3, layout=ops.LAYOUT_STREAM3)[1][0] for m, d, bs in SHAPES} == {1, 2, 4, 7, 8}
     assert {nw(m) for m, _, _ in SHAPES} == {1, 2, 4, 7, 8}
     assert nw(16384) == 4 and nw(32000) == 8 and nw(4112) == 2 and 257 % 2 and nw(27920) == 7 and 1745 % 7 and nw(28672) == 7
 
