@@ -472,18 +472,11 @@ template <int WT> int launch_syrk(float *A, int64_t d, int64_t prow0, int nk, in
     constexpr int BN = 32 * WT, LDW = BN + 16;
     const size_t lds = (size_t)2 * NB * LDW * sizeof(float);
     const int64_t rem = d - base, T = (rem + BN - 1) / BN;
-    auto kern = chol_syrk_kernel<WT>;
-    static QaPerDevice attr_done_dev;
-    const int attr_done_d = attr_done_dev.dev();
-    if ((attr_done_d < 0 || !attr_done_dev.done[attr_done_d])) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "cholesky_lt: cannot reserve %zu B of LDS", lds);
-        if constexpr (WT >= 2) {
-            if (hipFuncSetAttribute((const void *)chol_syrk_full_kernel<WT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                hipFuncSetAttribute((const void *)chol_syrk_full_kernel<WT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return qa_fail(QUIPAMD_ERR_LAUNCH, "cholesky_lt: cannot reserve %zu B of LDS", lds);
-        }
-        if (attr_done_d >= 0) attr_done_dev.done[attr_done_d] = true;
+    constexpr auto kern = chol_syrk_kernel<WT>;
+    if (int rc = qa_lds<kern>(lds, "cholesky_lt")) return rc;
+    if constexpr (WT >= 2) {
+        if (int rc = qa_lds<chol_syrk_full_kernel<WT, 1>>(lds, "cholesky_lt")) return rc;
+        if (int rc = qa_lds<chol_syrk_full_kernel<WT, 2>>(lds, "cholesky_lt")) return rc;
     }
     const unsigned grid = (unsigned)(strip ? T : T * (T + 1) / 2);
     if constexpr (WT >= 2) {

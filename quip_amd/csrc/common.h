@@ -4,6 +4,9 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+
 #include "quip_amd.h"
 
 // error reporting (capi.hip)
@@ -77,16 +80,31 @@ template <> struct DT<BF16> {
     default: return qa_fail(QUIPAMD_ERR_ARG, "bad dtype %d", (int)(dt));         \
     }
 
-// hipFuncSetAttribute is per DEVICE: one process driving several GPUs must raise the dynamic-LDS limit on each of them
-// (a per-process `static bool` made the second device's first launch fail).  One instance per kernel instantiation.
-struct QaPerDevice {
-    bool done[64] = {};
-    int dev() const
-    {
-        int d = 0;
-        (void)hipGetDevice(&d);
-        return (d >= 0 && d < 64) ? d : -1;
-    }
-};
+// ---- dynamic LDS ---------------------------------------------------------------------------------------------------
+constexpr size_t QA_LDS_DEFAULT = 64 * 1024;    // dynamic LDS a launch gets without asking
+constexpr size_t QA_LDS_MAX = 160 * 1024;       // one CU's LDS on gfx950
+
+// Raise the dynamic-LDS limit of Kern on the current device to at least `lds`: the one place that does it.  The attribute is per
+// DEVICE (a per-process flag made the second device's first launch fail) and per kernel, so the state is per instantiation of this
+// template and per device index, and holds the size reached: a larger request raises again, a smaller one returns after one
+// atomic load (acquire: the launch that follows relies on a raise another thread may have made).  Raising is serialised, so that
+// two threads asking for different sizes cannot leave the smaller one in force under the larger record.  Outside device 0..63
+// nothing is recorded and every call raises.
+template <auto Kern> int qa_lds(size_t lds, const char *who)
+{
+    if (lds <= QA_LDS_DEFAULT) return QUIPAMD_OK;
+    static std::atomic<size_t> reached[64];
+    static std::mutex raising;
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    const bool known = dev >= 0 && dev < 64;
+    if (known && lds <= reached[dev].load(std::memory_order_acquire)) return QUIPAMD_OK;
+    std::lock_guard<std::mutex> lock(raising);
+    if (known && lds <= reached[dev].load(std::memory_order_relaxed)) return QUIPAMD_OK;
+    if (hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return qa_fail(QUIPAMD_ERR_LAUNCH, "%s: cannot raise dynamic LDS to %zu", who, lds);
+    if (known) reached[dev].store(lds, std::memory_order_release);
+    return QUIPAMD_OK;
+}
 
 static inline int qa_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

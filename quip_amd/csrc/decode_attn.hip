@@ -185,16 +185,8 @@ int launch_attn(const void *q, const void *k, const void *v, void *kc, void *vc,
 {
     typedef typename DT<TI>::storage S;
     const size_t lds = (size_t)(maxlen + 8 + 4 * HD) * sizeof(float);
-    auto kern = decode_attn_kernel<TI, HD>;
-    static size_t reserved[64] = {};                                // per device and instantiation: the attribute is per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const bool known = dev >= 0 && dev < 64;
-    if (lds > 48 * 1024 && (!known || lds > reserved[dev])) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_attention: cannot reserve %zu B of LDS", lds);
-        if (known) reserved[dev] = lds;
-    }
+    constexpr auto kern = decode_attn_kernel<TI, HD>;
+    if (int rc = qa_lds<kern>(lds, "decode_attention")) return rc;
     kern<<<(unsigned)(bs * heads), 256, lds, s>>>((const S *)q, (const S *)k, (const S *)v, (S *)kc, (S *)vc, pos, (S *)out, heads,
                                                   maxlen, scale, ldq);
     QA_LAUNCH_CHECK("decode_attention");
@@ -568,7 +560,7 @@ __global__ __launch_bounds__(256 * NGRP) void decode_attn_u_kernel(AttnUArgs G)
 
 // LDS of a workgroup of the fused launch: the three operator images and the attention buffers of one wave group, of three with three heads per
 // workgroup (the 4-wave form holds what the one-head 12-wave form holds).  The launch, the choice of form and the maxlen query all read it here.
-constexpr size_t ATTN_U_LDS_MAX = 160 * 1024;
+constexpr size_t ATTN_U_LDS_MAX = QA_LDS_MAX;
 template <int HD, int P, int Q> size_t attn_u_lds(int64_t maxlen, bool three_heads)
 {
     return 3 * PassDims<P, Q, 4>::BYTES + (three_heads ? 3 : 1) * attn_u_group_bytes(HD, maxlen);
@@ -589,17 +581,9 @@ template <int HD, int P, int Q> int64_t attn_u_max_len(bool three_heads)
 template <int HD, int P, int Q, int NGRP, bool MH = false> int launch_attn_u_n(const AttnUArgs &A, int64_t bs, hipStream_t s)
 {
     const size_t lds = attn_u_lds<HD, P, Q>(A.maxlen, MH);
-    auto kern = decode_attn_u_kernel<HD, P, Q, NGRP, MH>;
-    static size_t reserved[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const bool known = dev >= 0 && dev < 64;
+    constexpr auto kern = decode_attn_u_kernel<HD, P, Q, NGRP, MH>;
     if (lds > ATTN_U_LDS_MAX) return qa_fail(QUIPAMD_ERR_SHAPE, "decode_attention_fused: %zu B of LDS (maxlen too large for this operator shape)", lds);
-    if (lds > 48 * 1024 && (!known || lds > reserved[dev])) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_attention_fused: cannot reserve %zu B of LDS", lds);
-        if (known) reserved[dev] = lds;
-    }
+    if (int rc = qa_lds<kern>(lds, "decode_attention_fused")) return rc;
     const int64_t wgs = bs * (MH ? (A.heads + 2) / 3 : A.heads);
     AttnUArgs Ap = A;
     Ap.pf = qa_pf_take();
@@ -693,14 +677,8 @@ template <int P, int Q> __global__ __launch_bounds__(1024) void u_only_kernel(UO
 template <int P, int Q> int launch_u_only(const UOnlyArgs &A, int64_t bs, hipStream_t s)
 {
     const size_t lds = PassDims<P, Q>::BYTES;
-    auto kern = u_only_kernel<P, Q>;
-    static QaPerDevice attr;
-    const int d = attr.dev();
-    if (lds > 48 * 1024 && (d < 0 || !attr.done[d])) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_u_only: cannot reserve %zu B of LDS", lds);
-        if (d >= 0) attr.done[d] = true;
-    }
+    constexpr auto kern = u_only_kernel<P, Q>;
+    if (int rc = qa_lds<kern>(lds, "decode_u_only")) return rc;
     kern<<<(unsigned)bs, 1024, lds, s>>>(A);
     QA_LAUNCH_CHECK("quipamd_decode_u_only");
     return QUIPAMD_OK;

@@ -417,9 +417,8 @@ extern "C" int quipamd_decode_bigp_u(const quipamd_bigp_u_op *ops, int nops, int
     hipStream_t s = (hipStream_t)stream;
 #define QA_BU(BS)                                                                                                                    \
     do {                                                                                                                             \
-        auto kern = bigp_u_kernel<BS>;                                                                                               \
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_bigp_u: cannot raise dynamic LDS to %zu", lds);                               \
+        constexpr auto kern = bigp_u_kernel<BS>;                                                                                     \
+        if (int rc = qa_lds<kern>(lds, "decode_bigp_u")) return rc;                                                                  \
         kern<<<grid, 64 * (nw > BS ? nw : BS), lds, s>>>(A);                                                                                          \
     } while (0)
     switch (rpg) {
@@ -471,17 +470,21 @@ extern "C" int quipamd_decode_bigp_v_gemm(const quipamd_bigp_v_gemm_args *a, voi
         nrt = 1;
         grid = dim3((unsigned)(p / 16), (unsigned)((a->rows + bs - 1) / bs));
     }
+#define QA_BV_K(BS, NRT, GT, B4)                                                                                                     \
+    do {                                                                                                                             \
+        constexpr auto kern = bigp_v_gemm_kernel<BS, NRT, GT, B4>;                                                                   \
+        if (int rc = qa_lds<kern>(lds, "decode_bigp_v_gemm")) return rc;                                                             \
+        kern<<<grid, 1024, lds, s>>>(A, two_over_maxq, c0);                                                                          \
+    } while (0)
 #define QA_BV(BS, NRT, GT)                                                                                                           \
     do {                                                                                                                             \
         /* (the 4-bit container with 16 rows AND 4 row tiles per wave does not fit the register file -- 20 bytes of scratch; the host  \
             picks 2 tiles per wave there, so that combination is never instantiated) */                                               \
         constexpr int B4_ = (BS > 4 && NRT == 4) ? 2 : 4;                                                                            \
-        auto kern = w4 ? bigp_v_gemm_kernel<BS, NRT, GT, B4_> : bigp_v_gemm_kernel<BS, NRT, GT, 2>;                                  \
         constexpr int XR_ = BS <= 4 ? BG_MAXBS : BG_MAXROWS, RG_ = BS < 4 ? BS : 4;                                                   \
         const size_t lds = (size_t)XR_ * 264 * 2 + 2 * XR_ * 4 + (size_t)16 * NRT * XR_ * 16 * 4 + (size_t)RG_ * nwp * 64 * sizeof(float4); \
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_bigp_v_gemm: cannot raise dynamic LDS to %zu", lds);                          \
-        kern<<<grid, 1024, lds, s>>>(A, two_over_maxq, c0);                                                                          \
+        if (w4) QA_BV_K(BS, NRT, GT, B4_);                                                                                           \
+        else QA_BV_K(BS, NRT, GT, 2);                                                                                                \
     } while (0)
 #define QA_BV_N(BS, GT)                                                                                                              \
     do {                                                                                                                             \
@@ -505,6 +508,7 @@ extern "C" int quipamd_decode_bigp_v_gemm(const quipamd_bigp_v_gemm_args *a, voi
 #undef QA_BV_B
 #undef QA_BV_N
 #undef QA_BV
+#undef QA_BV_K
     if (two_launch) {
         const int rc = quipamd_dequant_gemm(a->xt, QUIPAMD_F16, (const int32_t *)a->qweight, a->bits, QUIPAMD_LAYOUT_STREAM, QUIPAMD_QFN_B, a->scale, nullptr,
                                             nullptr, a->y, QUIPAMD_F32, 0, a->rows, a->m, (int64_t)p * 16, stream);

@@ -725,14 +725,8 @@ template <int P, int Q, int BITS> int launch_pair(const FusedArgs &A, float maxq
     typedef PassDims<P, Q> D;
     constexpr int NFR = (P / 16) * D::S0 + (Q / 16) * D::S1;
     const size_t lds = (size_t)2 * (D::N + 8) * 2 + D::ZT_B + D::Z1_B + (size_t)2 * NFR * 1024 + 2 * FG_NW * 4 + 64;
-    auto kern = fused_pair_kernel<P, Q, BITS>;
-    static QaPerDevice attr;
-    const int d = attr.dev();
-    if (d < 0 || !attr.done[d]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_fused_gemm (pair): cannot raise dynamic LDS to %zu", lds);
-        if (d >= 0) attr.done[d] = true;
-    }
+    constexpr auto kern = fused_pair_kernel<P, Q, BITS>;
+    if (int rc = qa_lds<kern>(lds, "decode_fused_gemm (pair)")) return rc;
     FusedArgs Ap = A;
     const unsigned gxp = (unsigned)(A.m / 16);
     Ap.pf = qa_pf_take();
@@ -756,14 +750,8 @@ template <int P, int Q, bool HAS_U, bool HAS_RES, int NORM, int RT, int CPW, int
 int launch_fused(const FusedArgs &A, int ngroups, hipStream_t s)
 {
     const size_t lds = fused_lds<P, Q, NRT, OPS>();
-    auto kern = fused_gemm_kernel<P, Q, HAS_U, HAS_RES, NORM, RT, CPW, NRT, YF32, BITS, OPS>;
-    static QaPerDevice attr;
-    const int d = attr.dev();
-    if (d < 0 || !attr.done[d]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_fused_gemm: cannot raise dynamic LDS to %zu", lds);
-        if (d >= 0) attr.done[d] = true;
-    }
+    constexpr auto kern = fused_gemm_kernel<P, Q, HAS_U, HAS_RES, NORM, RT, CPW, NRT, YF32, BITS, OPS>;
+    if (int rc = qa_lds<kern>(lds, "decode_fused_gemm")) return rc;
     const float maxq = g_fused_maxq;
     const unsigned gx = OPS ? (unsigned)A.bs : (unsigned)((A.m / 16 + RT * NRT - 1) / (RT * NRT));
     FusedArgs Ap = A;

@@ -320,14 +320,8 @@ template <int P, int Q, bool HAS_U, int NORM, bool YF32> int launch_head(const H
 {
     typedef PassDims<P, Q> D;
     const size_t lds = (size_t)HD_MAXBS * D::N * 2 + D::BYTES + (32 + 64 + 64) * 4;
-    auto kern = head_kernel<P, Q, HAS_U, NORM, YF32>;
-    static QaPerDevice attr;
-    const int d = attr.dev();
-    if (d < 0 || !attr.done[d]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "decode_head: cannot raise dynamic LDS to %zu", lds);
-        if (d >= 0) attr.done[d] = true;
-    }
+    constexpr auto kern = head_kernel<P, Q, HAS_U, NORM, YF32>;
+    if (int rc = qa_lds<kern>(lds, "decode_head")) return rc;
     kern<<<(unsigned)nwg, 1024, lds, s>>>(A);
     QA_LAUNCH_CHECK("quipamd_decode_head");
     return QUIPAMD_OK;

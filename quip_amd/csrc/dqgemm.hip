@@ -427,15 +427,9 @@ int launch_tile(const TileGroup &G, int ngroups, const EpiArgs &e, int64_t d, in
     typedef Deq<BITS> Q;
     constexpr int XB = 16 * Q::KC * 2;
     constexpr size_t lds = (size_t)CW * DEPTH * XB + (size_t)(CW * RT * 256 + CW * 64) * 4;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = dqgemm_tile_kernel<BITS, RT, CW, DEPTH>;
-    static QaPerDevice attr_set_dev;
-    const int attr_set_d = attr_set_dev.dev();
-    if ((attr_set_d < 0 || !attr_set_dev.done[attr_set_d]) && lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm: cannot raise dynamic LDS to %zu", lds);
-        if (attr_set_d >= 0) attr_set_dev.done[attr_set_d] = true;
-    }
+    static_assert(lds <= QA_LDS_MAX, "LDS budget");
+    constexpr auto kern = dqgemm_tile_kernel<BITS, RT, CW, DEPTH>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm")) return rc;
     const uint32_t nkc = (uint32_t)(d / Q::KC);
     const uint32_t cps = (nkc + S - 1) / S;
     const unsigned gz = (nkc + cps - 1) / cps;
@@ -452,15 +446,9 @@ int launch_cfg(const uint16_t *x, const uint4 *qw, const EpiArgs &e, int64_t d, 
     constexpr int PART = RT * BT * 5 * 64 * 4;
     constexpr int REGION = (BT * XB > PART) ? BT * XB : PART;
     constexpr size_t lds = (size_t)NW * REGION;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = dqgemm_kernel<BITS, RT, BT, NW>;
-    static QaPerDevice attr_set_dev;
-    const int attr_set_d = attr_set_dev.dev();
-    if ((attr_set_d < 0 || !attr_set_dev.done[attr_set_d]) && lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm: cannot raise dynamic LDS to %zu", lds);
-        if (attr_set_d >= 0) attr_set_dev.done[attr_set_d] = true;
-    }
+    static_assert(lds <= QA_LDS_MAX, "LDS budget");
+    constexpr auto kern = dqgemm_kernel<BITS, RT, BT, NW>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm")) return rc;
     const int64_t nby = (e.bs + 16 * BT - 1) / (16 * BT);
     QA_REQUIRE(nby <= 65535, QUIPAMD_ERR_SHAPE, "dequant_gemm: bs too large for this kernel (%lld)", (long long)e.bs);
     kern<<<dim3((unsigned)(e.m / 16 / RT), (unsigned)nby), 64 * NW, lds, s>>>(x, qw, e, d);

@@ -235,11 +235,9 @@ int launch_h2(const K2Args &A, hipStream_t s)
 {
     typedef DeqT<BITS, ACT> Q;
     constexpr size_t lds = (size_t)NW * NCH * (HALF ? 8 : 16) * Q::KC * 2;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = dq_h_kernel<BITS, ACT, RT, NW, NCH, HALF, EXACT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm: cannot raise dynamic LDS to %zu", lds);
+    static_assert(lds <= QA_LDS_MAX, "LDS budget");
+    constexpr auto kern = dq_h_kernel<BITS, ACT, RT, NW, NCH, HALF, EXACT>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm")) return rc;
     kern<<<dim3((unsigned)(A.e.m / 16 / RT)), 64 * NW, lds, s>>>(A);
     QA_LAUNCH_CHECK("quipamd_dequant_gemm(h)");
     return QUIPAMD_OK;
@@ -249,10 +247,8 @@ int launch_h2g(const K2GArgs &G, int ngroups, hipStream_t s)
 {
     typedef DeqT<BITS, ACT> Q;
     constexpr size_t lds = (size_t)NW * NCH * (HALF ? 8 : 16) * Q::KC * 2;
-    auto kern = dq_hg_kernel<BITS, ACT, RT, NW, NCH, HALF, EXACT>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm_grouped: cannot raise dynamic LDS to %zu", lds);
+    constexpr auto kern = dq_hg_kernel<BITS, ACT, RT, NW, NCH, HALF, EXACT>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm_grouped")) return rc;
     kern<<<dim3((unsigned)(G.g[0].e.m / 16 / RT), (unsigned)ngroups), 64 * NW, lds, s>>>(G);
     QA_LAUNCH_CHECK("quipamd_dequant_gemm_grouped(h)");
     return QUIPAMD_OK;
@@ -320,12 +316,10 @@ int launch_s(const K2Args &A, hipStream_t s)
 {
     constexpr int TPS = 256 / (512 / BITS);
     constexpr size_t lds = (size_t)D * KSP * SPW * (16 * 256 * 2 + NW * TPS * 1024);
-    static_assert(lds <= 160 * 1024, "LDS budget");
+    static_assert(lds <= QA_LDS_MAX, "LDS budget");
     QA_REQUIRE(A.e.m * A.d * BITS / 8 < ((int64_t)1 << 32), QUIPAMD_ERR_SHAPE, "dequant_gemm(s): packed weights >= 4 GiB");
-    auto kern = dq_s_kernel<BITS, ACT, NW, KSP, SPW, D>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm: cannot raise dynamic LDS to %zu", lds);
+    constexpr auto kern = dq_s_kernel<BITS, ACT, NW, KSP, SPW, D>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm")) return rc;
     const uint32_t ntile = (uint32_t)(A.e.m / 16);
     kern<<<dim3((ntile + NW - 1) / NW), 64 * (NW * KSP + 2), lds, s>>>(A, ntile);
     QA_LAUNCH_CHECK("quipamd_dequant_gemm(s)");
@@ -337,13 +331,11 @@ int launch_sg(const K2GArgs &G, int ngroups, hipStream_t s)
 {
     constexpr int TPS = 256 / (512 / BITS);
     constexpr size_t lds = (size_t)D * KSP * SPW * (16 * 256 * 2 + NW * TPS * 1024);
-    static_assert(lds <= 160 * 1024, "LDS budget");
+    static_assert(lds <= QA_LDS_MAX, "LDS budget");
     const K2Args &A = G.g[0];
     QA_REQUIRE(A.e.m * A.d * BITS / 8 < ((int64_t)1 << 32), QUIPAMD_ERR_SHAPE, "dequant_gemm_grouped(s): packed weights >= 4 GiB");
-    auto kern = dq_sg_kernel<BITS, ACT, NW, KSP, SPW, D>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm_grouped: cannot raise dynamic LDS to %zu", lds);
+    constexpr auto kern = dq_sg_kernel<BITS, ACT, NW, KSP, SPW, D>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm_grouped")) return rc;
     const uint32_t ntile = (uint32_t)(A.e.m / 16);
     kern<<<dim3((ntile + NW - 1) / NW, (unsigned)ngroups), 64 * (NW * KSP + 2), lds, s>>>(G, ntile);
     QA_LAUNCH_CHECK("quipamd_dequant_gemm_grouped(s)");
@@ -693,12 +685,10 @@ int launch_mb2(const K2Args &A, hipStream_t s)
 {
     constexpr int NB = WB * BTw * 16, ROWS = WR * RTw * 16, TPG = 256 / (512 / BITS);
     constexpr size_t lds = (size_t)2 * (NB * 512 + ROWS / 16 * TPG * 1024);
-    static_assert(lds <= 160 * 1024 && lds >= (size_t)NB * 8, "LDS budget");
+    static_assert(lds <= QA_LDS_MAX && lds >= (size_t)NB * 8, "LDS budget");
     QA_REQUIRE(A.e.m * A.d * BITS / 8 < ((int64_t)1 << 32), QUIPAMD_ERR_SHAPE, "dequant_gemm(mb): packed weights >= 4 GiB");
-    auto kern = dq_mb_kernel<BITS, ACT, WR, WB, RTw, BTw, NL, T32>;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm: cannot raise dynamic LDS to %zu", lds);
+    constexpr auto kern = dq_mb_kernel<BITS, ACT, WR, WB, RTw, BTw, NL, T32>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm")) return rc;
     const uint32_t nrb = (uint32_t)((A.e.m + ROWS - 1) / ROWS), nby = (uint32_t)((A.e.bs + NB - 1) / NB);
     const uint32_t nrb8 = (nrb + 7) / 8 * 8;                           // padded so that id -> (xcd, within) covers every row block
     const uint64_t nblk = (uint64_t)nrb8 * nby;

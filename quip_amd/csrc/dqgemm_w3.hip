@@ -71,7 +71,7 @@ template <int NW, int KSP, int SPW, int D> struct W3Cfg {
     static_assert(SPS % 2 == 0, "a high transfer covers two stages");
     static_assert(SPS * NI * (D - 2) < 64 && NWOPS * (D - 2) < 64 && D >= 2, "vmcnt range");
     static_assert(NCW * 1024 + NCW * 128 <= D * SB && NW <= 8, "exchange area");
-    static_assert(LDS <= 160 * 1024, "LDS budget");
+    static_assert(LDS <= QA_LDS_MAX, "LDS budget");
 };
 
 template <class ACT, int NW, int KSP, int SPW, int D>
@@ -255,15 +255,9 @@ template <class ACT, int NW, int KSP, int SPW, int D>
 int launch_w3(const K2Args &A, hipStream_t s)
 {
     constexpr size_t lds = W3Cfg<NW, KSP, SPW, D>::LDS;
-    auto kern = dq_w3_kernel<ACT, NW, KSP, SPW, D>;
-    static_assert(lds > 64 * 1024, "every configuration raises the dynamic LDS limit");
-    static QaPerDevice attr;                                           // once per device and instantiation, not per launch (common.h)
-    const int dv = attr.dev();
-    if (dv < 0 || !attr.done[dv]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm(STREAM3): cannot raise dynamic LDS to %zu", lds);
-        if (dv >= 0) attr.done[dv] = true;
-    }
+    constexpr auto kern = dq_w3_kernel<ACT, NW, KSP, SPW, D>;
+    static_assert(lds > QA_LDS_DEFAULT, "every configuration raises the dynamic LDS limit");
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm(STREAM3)")) return rc;
     const uint32_t ntile = (uint32_t)(A.e.m / 16);
     kern<<<dim3((ntile + NW - 1) / NW, (unsigned)((A.e.bs + 15) / 16)), 64 * (NW * KSP + 2), lds, s>>>(A, ntile);
     QA_LAUNCH_CHECK("quipamd_dequant_gemm(STREAM3)");

@@ -331,14 +331,8 @@ int g_gb_force_rows = 0;                                              // lab: ro
 template <int R> int gb_chain(const GbArgs &A, hipStream_t s)
 {
     const size_t lds = (size_t)(GB_NB * R + GB_NB * GB_NB + 2 * R + 4) * sizeof(float);
-    auto kern = gptqb_chain_kernel<R>;
-    static QaPerDevice attr;
-    const int dv = attr.dev();
-    if (lds > 64 * 1024 && (dv < 0 || !attr.done[dv])) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "gptq_round_qfnb: cannot raise dynamic LDS to %zu", lds);
-        if (dv >= 0) attr.done[dv] = true;
-    }
+    constexpr auto kern = gptqb_chain_kernel<R>;
+    if (int rc = qa_lds<kern>(lds, "gptq_round_qfnb")) return rc;
     kern<<<(unsigned)(A.G - g_gb_debug_short_grid > 0 ? A.G - g_gb_debug_short_grid : 1), GB_T, lds, s>>>(A);
     return QUIPAMD_OK;
 }
@@ -346,14 +340,8 @@ template <int R> int gb_chain(const GbArgs &A, hipStream_t s)
 template <int NC, bool XL, int NBK = GB_NB, int HP = 3> int gb_chainp(const GbArgs &A, int grid, hipStream_t s)
 {
     constexpr size_t lds = (size_t)(NBK * 64 * NC + NBK * NBK + 4) * sizeof(float);
-    auto kern = gptqb_chainp_kernel<NC, XL, NBK, HP>;
-    static QaPerDevice attr;
-    const int dv = attr.dev();
-    if (dv < 0 || !attr.done[dv]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "gptq_round_qfnb: cannot raise dynamic LDS to %zu", lds);
-        if (dv >= 0) attr.done[dv] = true;
-    }
+    constexpr auto kern = gptqb_chainp_kernel<NC, XL, NBK, HP>;
+    if (int rc = qa_lds<kern>(lds, "gptq_round_qfnb")) return rc;
     if (!XL) grid -= g_gb_debug_short_grid;                             // (XL: GbArgs.absent -- which blocks land on the XCD is not the host's to say)
     kern<<<(unsigned)(grid > 0 ? grid : 1), 64 * NC * (1 + HP), lds, s>>>(A);
     return QUIPAMD_OK;
@@ -361,10 +349,19 @@ template <int NC, bool XL, int NBK = GB_NB, int HP = 3> int gb_chainp(const GbAr
 template <int NC, bool XL, int NBK = GB_NB, int HP = 3> bool gb_chainp_fits(int64_t blocks, int ncu)
 {
     constexpr size_t lds = (size_t)(NBK * 64 * NC + NBK * NBK + 4) * sizeof(float);
-    auto kern = gptqb_chainp_kernel<NC, XL, NBK, HP>;
+    constexpr auto kern = gptqb_chainp_kernel<NC, XL, NBK, HP>;
     int per_cu = 0;
-    return hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+    return qa_lds<kern>(lds, "gptq_round_qfnb") == QUIPAMD_OK &&
            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 64 * NC * (1 + HP), lds) == hipSuccess && blocks <= (int64_t)per_cu * ncu;
+}
+// does a grid of R-row workgroups of the barrier-per-phase chain fit the device at once?
+template <int R> bool gb_chain_fits(int64_t m, int ncu)
+{
+    const size_t lds = (size_t)(GB_NB * R + GB_NB * GB_NB + 2 * R + 4) * sizeof(float);
+    constexpr auto kern = gptqb_chain_kernel<R>;
+    int per_cu = 0;
+    return qa_lds<kern>(lds, "gptq_round_qfnb") == QUIPAMD_OK &&
+           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, GB_T, lds) == hipSuccess && (m + R - 1) / R <= (int64_t)per_cu * ncu;
 }
 
 }   // namespace
@@ -404,13 +401,6 @@ extern "C" int quipamd_gptq_round_qfnb(float *WT_rev, const float *FT, int bits,
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
         return qa_fail(QUIPAMD_ERR_LAUNCH, "gptq_round_qfnb: cannot query the device");
-    auto fits = [&](int R, const void *kern) {
-        const size_t lds = (size_t)(GB_NB * R + GB_NB * GB_NB + 2 * R + 4) * sizeof(float);
-        if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, GB_T, lds) != hipSuccess) return false;
-        return (m + R - 1) / R <= (int64_t)per_cu * ncu;
-    };
     int R = 0;
     // form: 0 barrier-per-phase chain (rounds 3-5), 1 pipelined across the XCDs, 2 / 3 / 4 / 5 pipelined on one XCD with 1 / 2 / 4 / 8 chain waves
     // (64 / 128 / 256 / 512 rows) per workgroup
@@ -429,16 +419,16 @@ extern "C" int quipamd_gptq_round_qfnb(float *WT_rev, const float *FT, int bits,
     else if (form == 3) R = 128;
     else if (form == 4) R = 256;
     else if (form == 5) R = 512;
-    else if (g_gb_force_rows == 16 && fits(16, (const void *)gptqb_chain_kernel<16>)) R = 16;
-    else if (g_gb_force_rows == 32 && fits(32, (const void *)gptqb_chain_kernel<32>)) R = 32;
-    else if (g_gb_force_rows == 64 && fits(64, (const void *)gptqb_chain_kernel<64>)) R = 64;
-    else if (g_gb_force_rows == 128 && fits(128, (const void *)gptqb_chain_kernel<128>)) R = 128;
+    else if (g_gb_force_rows == 16 && gb_chain_fits<16>(m, ncu)) R = 16;
+    else if (g_gb_force_rows == 32 && gb_chain_fits<32>(m, ncu)) R = 32;
+    else if (g_gb_force_rows == 64 && gb_chain_fits<64>(m, ncu)) R = 64;
+    else if (g_gb_force_rows == 128 && gb_chain_fits<128>(m, ncu)) R = 128;
     // (round 4 A/B, profiles/r04d_gptq_qfnb_rows.jsonl: the per-column all-gather over G = m / R granules is the cost, and 64 rows per workgroup
     //  beat 16 / 32 from 2048 rows on -- 2048^2 3.64 -> 3.08 us per column, 4096^2 4.16 -> 3.83, 8192 x 2048 4.86 -> 4.08, 2048 x 8192 4.02 -> 3.51)
-    else if (m < 1024 && fits(16, (const void *)gptqb_chain_kernel<16>)) R = 16;
-    else if (m < 2048 && fits(32, (const void *)gptqb_chain_kernel<32>)) R = 32;
-    else if (m <= 128 * 128 && fits(64, (const void *)gptqb_chain_kernel<64>)) R = 64;
-    else if (fits(128, (const void *)gptqb_chain_kernel<128>)) R = 128;
+    else if (m < 1024 && gb_chain_fits<16>(m, ncu)) R = 16;
+    else if (m < 2048 && gb_chain_fits<32>(m, ncu)) R = 32;
+    else if (m <= 128 * 128 && gb_chain_fits<64>(m, ncu)) R = 64;
+    else if (gb_chain_fits<128>(m, ncu)) R = 128;
     QA_REQUIRE(R != 0, QUIPAMD_ERR_UNSUPPORTED, "gptq_round_qfnb: %lld rows do not fit this device as one grid of co-resident workgroups (%d CUs)",
                (long long)m, ncu);
     const int64_t G = (m + R - 1) / R;

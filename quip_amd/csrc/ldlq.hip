@@ -417,14 +417,8 @@ static int launch_ldlq(const float *Wgrid, const float *LT, const float *eta, in
     const int64_t rounds1 = ((m + 15) / 16 + 255) / 256, rounds2 = ((m + 31) / 32 + 255) / 256;
     const bool rg2 = (g_ldlq_rg == 2) || (g_ldlq_rg == 0 && m >= 8192 && 13 * rounds2 < 8 * rounds1);
     const size_t lds1 = (size_t)(BS * LDS_LD + 16 * BS) * sizeof(float) + 4 * 3 * SLAB, lds2 = (size_t)(BS * LDS_LD + 32 * BS) * sizeof(float) + 4 * 4 * SLAB;
-    static QaPerDevice attr_set_dev;                                  // per instantiation
-    const int attr_set_d = attr_set_dev.dev();
-    if ((attr_set_d < 0 || !attr_set_dev.done[attr_set_d])) {
-        if (hipFuncSetAttribute((const void *)ldlq_kernel<MODE, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1) != hipSuccess ||
-            hipFuncSetAttribute((const void *)ldlq_kernel<MODE, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "%s: cannot raise dynamic LDS to %zu", who, lds2);
-        if (attr_set_d >= 0) attr_set_dev.done[attr_set_d] = true;
-    }
+    if (int rc = qa_lds<ldlq_kernel<MODE, 1>>(lds1, who)) return rc;
+    if (int rc = qa_lds<ldlq_kernel<MODE, 2>>(lds2, who)) return rc;
     if (rg2) ldlq_kernel<MODE, 2><<<(unsigned)((m + 31) / 32), 512, lds2, (hipStream_t)stream>>>(A);
     else ldlq_kernel<MODE, 1><<<(unsigned)((m + 15) / 16), 512, lds1, (hipStream_t)stream>>>(A);
     QA_LAUNCH_CHECK(who);

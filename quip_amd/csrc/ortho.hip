@@ -236,7 +236,7 @@ int launch_stage(StageArgs A, hipStream_t s)
     A.NT = (A.Pm + 15) / 16;
     A.RS = 16 * A.NT + 4;                                   // 16-byte aligned rows, consecutive rows 4 slots apart
     const int64_t per_c = 2ll * 16 * A.RS * 4;              // bytes of LDS per value of c (input + output tile)
-    QA_REQUIRE(per_c <= 160 * 1024, QUIPAMD_ERR_SHAPE, "ortho_apply_rows: factor size %d needs %lld B of LDS", A.Pm, (long long)per_c);
+    QA_REQUIRE(per_c <= (int64_t)QA_LDS_MAX, QUIPAMD_ERR_SHAPE, "ortho_apply_rows: factor size %d needs %lld B of LDS", A.Pm, (long long)per_c);
     int qb = 16;
     while (qb > 1 && qb * per_c > 72 * 1024) qb >>= 1;      // two workgroups per CU when possible
     const int64_t rgroups = (A.rows + 15) / 16;
@@ -244,10 +244,8 @@ int launch_stage(StageArgs A, hipStream_t s)
     while (qb > 1 && qb / 2 >= A.Po) qb >>= 1;
     A.QB = qb;
     const size_t lds = (size_t)(qb * per_c);
-    auto kern = ortho_stage_kernel<TI, TO>;
-    if (lds > 64 * 1024)
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "ortho: cannot raise dynamic LDS to %zu", lds);
+    constexpr auto kern = ortho_stage_kernel<TI, TO>;
+    if (int rc = qa_lds<kern>(lds, "ortho")) return rc;
     QA_REQUIRE(rgroups <= 65535, QUIPAMD_ERR_SHAPE, "ortho_apply_rows: too many rows (%lld)", (long long)A.rows);
     kern<<<dim3((unsigned)((A.Po + qb - 1) / qb), (unsigned)rgroups), 256, lds, s>>>(A);
     QA_LAUNCH_CHECK("quipamd_ortho_apply_rows");

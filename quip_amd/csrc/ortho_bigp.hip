@@ -231,10 +231,8 @@ extern "C" int quipamd_ortho_apply_bigp(const quipamd_small_op *ops, const int32
     hipStream_t s = (hipStream_t)stream;
 #define QA_BIGP(SD, RS)                                                                                                              \
     do {                                                                                                                             \
-        auto kern = ortho_bigp_kernel<SD, RS>;                                                                                       \
-        if (lds > 64 * 1024 &&                                                                                                       \
-            hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)             \
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "ortho_apply_bigp: cannot raise dynamic LDS to %zu", lds);                            \
+        constexpr auto kern = ortho_bigp_kernel<SD, RS>;                                                                             \
+        if (int rc = qa_lds<kern>(lds, "ortho_apply_bigp")) return rc;                                                               \
         kern<<<grid, BT, lds, s>>>(B);                                                                                               \
     } while (0)
     if (side == 0 && res) QA_BIGP(0, true);

@@ -704,17 +704,8 @@ template <class IN, class OUT, bool FUSED = false, int MAXI = 8, int NJ = 0> int
         }
     }
     const size_t lds = blk_lds(S, FUSED);
-    auto kern = blk_stage_kernel<IN, OUT, FUSED, MAXI, NJ>;
-    if (lds > 64 * 1024) {
-        static QaPerDevice attr;
-        static size_t raised[64] = {};
-        const int dv = attr.dev();
-        if (dv < 0 || raised[dv] < lds) {
-            if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return qa_fail(QUIPAMD_ERR_LAUNCH, "ortho_blocked_rows: cannot raise dynamic LDS to %zu", lds);
-            if (dv >= 0) raised[dv] = lds;
-        }
-    }
+    constexpr auto kern = blk_stage_kernel<IN, OUT, FUSED, MAXI, NJ>;
+    if (int rc = qa_lds<kern>(lds, "ortho_blocked_rows")) return rc;
     kern<<<dim3((unsigned)(G * (P / 16)), (unsigned)nops, (unsigned)((S.rows + BK_MAXR - 1) / BK_MAXR)), BK_T, lds, s>>>(SS);
     return QUIPAMD_OK;
 }

@@ -231,10 +231,8 @@ template <class TI, class TO, int NPASS, int CP, int CQ>
 int launch_split_pq(const SmallBatch &B, int ny, int64_t rows, hipStream_t s, const char *who)
 {
     const size_t lds = small_split_lds(B.op[0].p, B.op[0].q);
-    auto kern = ortho_small_split_kernel<TI, TO, NPASS, CP, CQ>;
-    if (lds > 64 * 1024)
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "%s: cannot raise dynamic LDS to %zu", who, lds);
+    constexpr auto kern = ortho_small_split_kernel<TI, TO, NPASS, CP, CQ>;
+    if (int rc = qa_lds<kern>(lds, who)) return rc;
     // NPASS == 1: workgroups walk the rows (factors loaded once each); a chain keeps one workgroup per row
     const unsigned gx = (unsigned)(NPASS == 1 && rows > 1024 ? 1024 : rows);
     kern<<<dim3(gx, (unsigned)ny), 1024, lds, s>>>(B);
@@ -265,10 +263,8 @@ int launch_small(const SmallBatch &B, int nops, int64_t rows, hipStream_t s)
 {
     if (B.op[0].M0_hi) return launch_split<TI, TO, 1>(B, nops, rows, s, "quipamd_ortho_apply_small");
     const size_t lds = small_lds(B.op[0].p, B.op[0].q);
-    auto kern = ortho_small_kernel<TI, TO>;
-    if (lds > 64 * 1024)
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "ortho_apply_small: cannot raise dynamic LDS to %zu", lds);
+    constexpr auto kern = ortho_small_kernel<TI, TO>;
+    if (int rc = qa_lds<kern>(lds, "ortho_apply_small")) return rc;
     kern<<<dim3((unsigned)(rows > 1024 ? 1024 : rows), (unsigned)nops), 1024, lds, s>>>(B);
     QA_LAUNCH_CHECK("quipamd_ortho_apply_small");
     return QUIPAMD_OK;
@@ -282,7 +278,7 @@ extern "C" int quipamd_ortho_apply_small_ops(const quipamd_small_op *ops, int no
     const int p = ops[0].p, q = ops[0].q, x_dtype = ops[0].x_dtype, out_dtype = ops[0].out_dtype;
     QA_REQUIRE(p >= 16 && q >= 16 && p % 16 == 0 && q % 16 == 0, QUIPAMD_ERR_SHAPE,
                "ortho_apply_small: p and q must be multiples of 16 (p=%d q=%d); use quipamd_ortho_apply_rows", p, q);
-    QA_REQUIRE(small_lds(p, q) <= 160 * 1024, QUIPAMD_ERR_SHAPE, "ortho_apply_small: factors + row need %zu B of LDS (> 160 KiB)", small_lds(p, q));
+    QA_REQUIRE(small_lds(p, q) <= QA_LDS_MAX, QUIPAMD_ERR_SHAPE, "ortho_apply_small: factors + row need %zu B of LDS (> 160 KiB)", small_lds(p, q));
     QA_REQUIRE((int64_t)p * q <= 16 * 1024, QUIPAMD_ERR_SHAPE, "ortho_apply_small: n = %d > 16384", p * q);
     QA_REQUIRE((q & (q - 1)) == 0, QUIPAMD_ERR_SHAPE, "ortho_apply_small: q = %d must be a power of two; use quipamd_ortho_apply_rows", q);
     QA_REQUIRE(rows >= 0 && rows < ((int64_t)1 << 31), QUIPAMD_ERR_SHAPE, "ortho_apply_small: bad row count");
@@ -290,7 +286,7 @@ extern "C" int quipamd_ortho_apply_small_ops(const quipamd_small_op *ops, int no
     const bool split = ops[0].M0_hi != nullptr;
     if (split) {
         QA_REQUIRE(p % 32 == 0 && q % 32 == 0, QUIPAMD_ERR_SHAPE, "ortho_apply_small: split-bf16 factors need p, q multiples of 32");
-        QA_REQUIRE(small_split_lds(p, q) <= 160 * 1024 && 2 * q >= p, QUIPAMD_ERR_SHAPE,
+        QA_REQUIRE(small_split_lds(p, q) <= QA_LDS_MAX && 2 * q >= p, QUIPAMD_ERR_SHAPE,
                    "ortho_apply_small: split-bf16 images need %zu B of LDS and q >= p/2", small_split_lds(p, q));
     }
     SmallBatch B;
@@ -330,7 +326,7 @@ extern "C" int quipamd_ortho_apply_small_chain(const quipamd_small_op *first, co
                "ortho_apply_small_chain: 1..%d second ops", QUIPAMD_SMALL_MAX_OPS - 1);
     const int p = first->p, q = first->q;
     QA_REQUIRE(p >= 32 && q >= 32 && p % 32 == 0 && q % 32 == 0 && (q & (q - 1)) == 0 && 2 * q >= p && (int64_t)p * q <= 16 * 1024 &&
-                   small_split_lds(p, q) <= 160 * 1024,
+                   small_split_lds(p, q) <= QA_LDS_MAX,
                QUIPAMD_ERR_SHAPE, "ortho_apply_small_chain: p=%d q=%d not supported by the split-bf16 single-launch kernel", p, q);
     QA_REQUIRE(first->M0_hi && first->M0_lo && first->M1_hi && first->M1_lo && first->x, QUIPAMD_ERR_ARG,
                "ortho_apply_small_chain: first op needs x and the four split-bf16 factor arrays");

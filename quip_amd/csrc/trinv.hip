@@ -147,14 +147,7 @@ extern "C" int quipamd_unit_upper_inverse(const float *N, float *X, float *work,
     QA_REQUIRE(N && X && work && N != X && work != X && work != N, QUIPAMD_ERR_ARG, "unit_upper_inverse: three distinct buffers wanted");
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)(TB * (TB + 1) + TB * TB) * sizeof(float);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        if (hipFuncSetAttribute((const void *)trinv_diag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "unit_upper_inverse: cannot raise dynamic LDS to %zu", lds);
-        attr_set[dev] = true;
-    }
+    if (int rc = qa_lds<trinv_diag_kernel>(lds, "unit_upper_inverse")) return rc;
     trinv_diag_kernel<<<(unsigned)((d + TB - 1) / TB), TB, lds, s>>>(N, X, d);
     for (int64_t b = TB; b < d; b *= 2) {
         const unsigned pairs = (unsigned)((d + 2 * b - 1) / (2 * b));

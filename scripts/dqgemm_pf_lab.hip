@@ -242,14 +242,8 @@ template <class ACT, int TM, int TN> int launch_pf(const PfArgs &A0, hipStream_t
     PfArgs A = A0;
     A.ntm = (uint32_t)(A.m / TM);
     const size_t lds = (size_t)2 * (TM + TN) * 128 + TN * 4;
-    auto kern = dq_pf_kernel<ACT, TM, TN>;
-    static QaPerDevice attr;
-    const int d = attr.dev();
-    if (d < 0 || !attr.done[d]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return qa_fail(QUIPAMD_ERR_LAUNCH, "dequant_gemm (prefill): cannot raise dynamic LDS to %zu", lds);
-        if (d >= 0) attr.done[d] = true;
-    }
+    constexpr auto kern = dq_pf_kernel<ACT, TM, TN>;
+    if (int rc = qa_lds<kern>(lds, "dequant_gemm (prefill)")) return rc;
     const unsigned grid = A.ntm * (unsigned)((A.bs + TN - 1) / TN);
     kern<<<grid, 256, lds, s>>>(A);
     QA_LAUNCH_CHECK("quipamd_dequant_gemm (prefill)");

@@ -36,6 +36,33 @@ def test_matches_eager_chain(dtype, bs, heads, hd, maxlen, pos):
     assert (got.double() - want).abs().max().item() <= tol * max(1.0, want.abs().max().item())
 
 
+def test_cache_lengths_around_the_default_lds_limit_then_a_short_one():
+    """One process, in this order: maxlen 14000, 16120, 16121, then 64 (hd 64, fp16: (maxlen + 8 + 256) * 4 B of dynamic LDS).  57 056 B is
+    under the 64 KiB a launch gets without asking, 65 536 B is exactly that limit and must run without a raise as well, 65 540 B is the
+    first size that must be raised, and the short cache afterwards runs under the limit the long one left.
+    Gates: test_plain_attention_at_its_cap's (tests/test_gpu_decode_attn_long.py) for fp16."""
+    from quip_amd import ops
+    bs, heads, hd, dtype = 1, 2, 64, torch.float16
+    tol, rtol = 2e-3, 2e-3
+    lds = {14000: 57056, 16120: 65536, 16121: 65540, 64: 1312}
+    for maxlen in (14000, 16120, 16121, 64):
+        assert (maxlen + 8 + 4 * hd) * 4 == lds[maxlen]
+        pos = maxlen - 1
+        g = torch.Generator().manual_seed(maxlen)
+        mk = lambda *s: torch.randn(*s, generator=g).to(dtype).to(DEV)
+        q, k, v = mk(bs, heads * hd), mk(bs, heads * hd), mk(bs, heads * hd)
+        kc, vc = mk(bs, heads, maxlen, hd), mk(bs, heads, maxlen, hd)
+        want, kc_w, vc_w = _ref(q, k, v, kc, vc, pos)
+        got = ops.decode_attention(q, k, v, kc, vc, torch.tensor([pos], dtype=torch.int64, device=DEV))
+        assert torch.equal(kc, kc_w) and torch.equal(vc, vc_w), maxlen
+        err = (got.double() - want).abs().max().item()
+        w = want.view(bs, heads, hd)
+        rel = float(((got.double().view(bs, heads, hd) - w).norm(dim=-1) / w.norm(dim=-1)).max())
+        print(f"plain attention hd {hd} fp16 maxlen {maxlen} ({lds[maxlen]} B of LDS): max abs err {err:.2e}, worst rel l2 {rel:.2e} (gates {tol}, {rtol})")
+        assert err <= tol * max(1.0, want.abs().max().item()), (maxlen, err)
+        assert rel <= rtol, (maxlen, rel)
+
+
 def test_graph_replay_advances_with_the_device_position():
     from quip_amd import ops
     bs, heads, hd, maxlen = 1, 4, 64, 64
