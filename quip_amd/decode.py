@@ -518,9 +518,51 @@ def best_mode(dec, bs, dtype, max_len=None):
     return "plain"
 
 
+class Sampling:
+    """how DecodeEngine picks a token: temperature, top-k and top-p (Hugging Face's TopKLogitsWarper, then TopPLogitsWarper) and the 64-bit
+    seed of the draws -- ops.sample_rows has the arithmetic.  temperature 0 or top_k 1 is greedy.  A plain value: validated here, compared by
+    value, no GPU involved.  Not served: EOS / stop handling, repetition penalties, per-sequence parameters, beam search."""
+    __slots__ = ("temperature", "top_k", "top_p", "seed")
+
+    def __init__(self, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        try:
+            t, p = float(temperature), float(top_p)
+        except (TypeError, ValueError):
+            raise ValueError(f"Sampling: temperature and top_p must be numbers (got {temperature!r}, {top_p!r})") from None
+        if not t >= 0.0 or t == float("inf"):
+            raise ValueError(f"Sampling: temperature must be a finite number >= 0 (0: greedy), got {temperature!r}")
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"Sampling: top_p must lie in (0, 1] (1: off), got {top_p!r}")
+        if not is_int(top_k) or top_k < 0:
+            raise ValueError(f"Sampling: top_k must be an integer >= 0 (0: off), got {top_k!r}")
+        if not is_int(seed) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"Sampling: seed must be an integer in [0, 2^64), got {seed!r}")
+        for name, v in zip(self.__slots__, (t, int(top_k), p, int(seed))):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Sampling is immutable: build a new one")
+
+    def _key(self):
+        return (self.temperature, self.top_k, self.top_p, self.seed)
+
+    def __eq__(self, other):
+        return isinstance(other, Sampling) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Sampling(temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p}, seed={self.seed})"
+
+
 class DecodeEngine:
     """benchmark()'s per-token loop as ONE hipGraph replay per token: static KV cache [bs, kv_heads, max_len, hd] per block, position and
-    current token on the device.  `forward(ids)` is `model(ids, past_key_values=...)` for the next position; `generate` is greedy."""
+    current token on the device.  `forward(ids)` is `model(ids, past_key_values=...)` for the next position; `generate` is greedy unless a
+    `Sampling` is set (set_sampling, or generate's `sampling=`): then every step ends with one sample launch (ops.sample_rows) instead of
+    the argmax, replayed from a second graph.  The draw for the token fed at cache position t of sequence b is Philox(seed; t, b): the same
+    seed gives the same tokens with or without the graph, after prefill() or token-by-token feeding, and again after reset()."""
 
     def __init__(self, decoder, bs=1, max_len=2048, mode="auto", graph=True):
         self.dec = decoder
@@ -553,6 +595,13 @@ class DecodeEngine:
         self._graph = None
         self._want_graph = graph
         self._steps = 0
+        self._sampling = None            # None: greedy -- the launch sequence of _one() below, untouched by anything sampling adds
+        self._sample_params = None       # the device struct of the sample launch (ops.sample_params), made by the first set_sampling(Sampling)
+        self._graph_sampled = None       # the sampled step's graph, captured by the first sampled step
+        self._sampling_written = None    # what the device struct holds
+        self.logprob = torch.zeros(bs, dtype=torch.float32, device=self.dev)     # log-probability of the token of the last sampled step
+        self.kept_n = torch.zeros(bs, dtype=torch.int32, device=self.dev)        # ... how many entries survived top-k / top-p in that step,
+        self.kept_mass = torch.ones(bs, dtype=torch.float32, device=self.dev)    # ... and their share of the top-k mass
 
     @classmethod
     def from_hf(cls, model, packed=None, bs=1, max_len=2048, mode="auto", graph=True, device=None):
@@ -568,7 +617,45 @@ class DecodeEngine:
         return cls(dec, bs=bs, max_len=max_len, mode=mode, graph=graph)
 
     # -- one step ---------------------------------------------------------------------------------
+    @property
+    def sampling(self):
+        return self._sampling
+
+    def set_sampling(self, sampling):
+        """None: greedy (the default).  A `Sampling`: every following step, and the end of prefill(), draws its token with these parameters.
+        The parameters live in one device struct that the sample launch reads at run time: changing them rewrites the struct (one small copy)
+        and never recaptures the sampled graph."""
+        if sampling is not None and not isinstance(sampling, Sampling):
+            raise TypeError(f"DecodeEngine.set_sampling: a decode.Sampling or None (got {type(sampling).__name__})")
+        if sampling is not None:
+            args = (sampling.temperature, sampling.top_k, sampling.top_p, sampling.seed)
+            if self._sample_params is None:
+                self._sample_params = ops.sample_params(*args, device=self.dev)
+            elif sampling != self._sampling_written:
+                ops.write_sample_params(self._sample_params, *args)
+            self._sampling_written = sampling
+        self._sampling = sampling
+
+    def _sample(self):
+        """the sample launch: counter = the device position, which by now is the cache position the drawn token will be fed at"""
+        ops.sample_rows(self.logits, self._sample_params, self.pos, out=self.ids, logprob=self.logprob, kept_n=self.kept_n, kept_mass=self.kept_mass,
+                        clear=self.part_idx if self._fh else None)
+
+    def _one_sampled(self):
+        if self.attn_workspace is not None:
+            self.dec.attn_workspace = self.attn_workspace
+        if self._fh:                                     # the head launch wrote fp16 `logits` and advanced pos; clearing its argmax partials makes
+            self.dec.step_fused_head(self.ids, self.pos, self.caches, self.logits, self.part_val, self.part_idx)     # the next embed launch read `ids`
+            self._sample()
+            return
+        lg = self.dec.step(self.ids, self.pos, self.caches, self.arange)
+        self.logits.copy_(lg)
+        self.pos.add_(1)
+        self._sample()
+
     def _one(self):
+        if self._sampling is not None:
+            return self._one_sampled()
         if self.attn_workspace is not None:              # (a decoder may serve several engines: each step brings its own)
             self.dec.attn_workspace = self.attn_workspace
         if self._fh:
@@ -585,9 +672,46 @@ class DecodeEngine:
         if self._fh:
             self.part_idx.fill_(-1)
 
+    def _state(self):
+        ts = [self.pos, self.ids, self.logits, self.logprob]
+        return ts + [self.part_val, self.part_idx] if self._fh else ts
+
+    @torch.no_grad()
+    def _capture_in_place(self):
+        """capture _one() as it stands at the engine's CURRENT position: position, token, logits and partials are put back after each of the
+        two warm-up steps and after the capture.  (The warm-up steps write the cache row of the current position, which the step that
+        follows writes anyway.)"""
+        saved = [t.clone() for t in self._state()]
+
+        def restore():
+            for t, s in zip(self._state(), saved):
+                t.copy_(s)
+        self._one()
+        restore()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._one()
+            restore()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._one()
+        restore()
+        return g
+
     @torch.no_grad()
     def _prepare(self):
-        if self._graph is not None or not self._want_graph:
+        if not self._want_graph:
+            return
+        if self._sampling is not None:                   # the sampled step is a launch sequence of its own: a second graph, captured on first use
+            if self._graph_sampled is None:
+                self._graph_sampled = self._capture_in_place()
+            return
+        if self._graph is not None:
+            return
+        if self._steps:                                  # first greedy step of an engine that has only sampled so far: nothing may be reset
+            self._graph = self._capture_in_place()
             return
         keep = self.ids.clone()
         self._one()                                      # warm-up (allocator, table builds); the caches are rewritten from position 0
@@ -611,8 +735,9 @@ class DecodeEngine:
         if self._steps >= self.max_len:
             raise RuntimeError("DecodeEngine: KV cache full (max_len %d)" % self.max_len)
         self._prepare()
-        if self._graph is not None:
-            self._graph.replay()
+        g = self._graph if self._sampling is None else self._graph_sampled
+        if g is not None:
+            g.replay()
         else:
             self._one()
         self._steps += 1
@@ -680,7 +805,10 @@ class DecodeEngine:
                 outs.append(lg)
         last = lg[:, -1] if all_logits else lg
         self.logits.copy_(last)
-        ops.argmax_rows(self.logits, out=self.ids)
+        if self._sampling is None:
+            ops.argmax_rows(self.logits, out=self.ids)
+        else:
+            self._sample()                               # pos is behind the prompt by now: the position the drawn token is fed at
         if self._fh:
             self.part_idx.fill_(-1)                      # the next step's embed launch reads `ids`, not the partials of an earlier step
         self._steps += n
@@ -714,22 +842,31 @@ class DecodeEngine:
         return float(torch.exp(torch.stack(nlls).sum() / (nsamples * seqlen)))
 
     @torch.no_grad()
-    def generate(self, first, n):
-        """greedy continuation: returns int64 [n, bs] -- the n tokens following `first` (model.generate(do_sample=False) with a cache).
+    def generate(self, first, n, sampling=None):
+        """continuation: returns int64 [n, bs] -- the n tokens following `first`.  Greedy (model.generate(do_sample=False) with a cache) unless
+        a `Sampling` is in force: the engine's (set_sampling), or `sampling`, which applies to this call only -- the previous setting is put
+        back afterwards, also when the call raises.
         `first`: one token per sequence (int or [bs]), or a prompt [bs, n_prompt], which is prefilled in one pass."""
+        if sampling is not None:
+            prev = self._sampling
+            self.set_sampling(sampling)
+            try:
+                return self.generate(first, n)
+            finally:
+                self.set_sampling(prev)
         if torch.is_tensor(first) and first.dim() == 2 and first.shape[1] > 1:
             self.prefill(first)
         else:
             self.forward(first)
         out = []
         for i in range(n):
-            if self._fh:                                 # the embed launch of step i + 1 writes step i's argmax into `ids`
+            if self._fh and self._sampling is None:      # the embed launch of step i + 1 writes step i's argmax into `ids`
                 if i == n - 1:
                     out.append(self.logits.float().argmax(-1))
                 else:
                     self.step()
                     out.append(self.ids.clone())
-            else:                                        # the step itself leaves its argmax in `ids`
+            else:                                        # the step itself leaves its token (argmax, or the sample launch's draw) in `ids`
                 out.append(self.ids.clone())
                 if i < n - 1:
                     self.step()

@@ -1310,6 +1310,67 @@ def argmax_rows(x, out=None):
     return out
 
 
+class SampleParams(ctypes.Structure):
+    """mirror of `quipamd_sample_params` (include/quip_amd_sample.h)"""
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("top_k", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
+
+
+SAMPLE_PARAMS_BYTES = ctypes.sizeof(SampleParams)     # 24
+
+
+def _sample_params_host(temperature, top_k, top_p, seed):
+    sp = SampleParams(float(temperature), float(top_p), max(-1, min(int(top_k), 0x7fffffff)), 0, int(seed) & 0xffffffffffffffff)
+    return torch.frombuffer(bytearray(bytes(sp)), dtype=torch.uint8)
+
+
+def write_sample_params(t, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    """rewrite the `quipamd_sample_params` held by t (uint8 [24] on the device) in place: one small host-to-device copy on the current
+    stream.  The sample launch reads the struct at run time, so a captured graph that holds the launch follows the change."""
+    _need_gpu(t)
+    assert t.dtype == torch.uint8 and t.numel() == SAMPLE_PARAMS_BYTES and t.is_contiguous() and t.data_ptr() % 8 == 0
+    t.copy_(_sample_params_host(temperature, top_k, top_p, seed))
+    return t
+
+
+def sample_params(temperature=1.0, top_k=0, top_p=1.0, seed=0, device=None):
+    """a uint8 [24] device tensor holding a `quipamd_sample_params`: temperature (<= 0: greedy), top_k (<= 0 or >= n: off), top_p (>= 1: off)
+    and the 64-bit Philox seed"""
+    t = torch.empty(SAMPLE_PARAMS_BYTES, dtype=torch.uint8, device=device)
+    return write_sample_params(t, temperature, top_k, top_p, seed)
+
+
+def sample_rows(logits, params, counter, out=None, logprob=None, kept_n=None, kept_mass=None, clear=None):
+    """out[r] = one token of row r of `logits` ([rows, n] f32 / f16 / bf16, any row stride and alignment, n <= 262144) by temperature /
+    top-k / top-p sampling, one launch (quipamd_sample_rows, include/quip_amd_sample.h has the contract).  params: sample_params(); counter:
+    int64 [1] on the device -- the draw of row r is Philox4x32-10 of (seed; counter, r), nothing else, so equal inputs give equal outputs.
+    Also written: logprob fp32 [rows] (the token's log-probability among the survivors), kept_n int32 [rows] (survivors of top-k / top-p),
+    kept_mass fp32 [rows] (their share of the top-k mass); clear: int32 [rows, m], set to -1 (the argmax partials of decode_head).
+    Returns (out, logprob, kept_n, kept_mass)."""
+    _need_gpu(logits, params, counter, out, logprob, kept_n, kept_mass, clear)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows, n = logits.shape
+    assert params.dtype == torch.uint8 and params.numel() == SAMPLE_PARAMS_BYTES and params.is_contiguous() and params.data_ptr() % 8 == 0
+    assert counter.dtype == torch.int64 and counter.numel() == 1
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    if logprob is None:
+        logprob = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if kept_n is None:
+        kept_n = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    if kept_mass is None:
+        kept_mass = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    for t, dt in ((out, torch.int64), (logprob, torch.float32), (kept_n, torch.int32), (kept_mass, torch.float32)):
+        assert t.dtype == dt and t.numel() == rows and t.is_contiguous()
+    clear_n = 0
+    if clear is not None:
+        assert clear.dtype == torch.int32 and clear.dim() == 2 and clear.shape[0] == rows and clear.is_contiguous()
+        clear_n = clear.shape[1]
+    _lib.call("quipamd_sample_rows", _p(logits), _dtype(logits), rows, n, logits.stride(0) if rows > 1 else max(n, logits.stride(0)),
+              _p(params), _p(counter), _p(out), _p(logprob), _p(kept_n), _p(kept_mass), _p(clear), clear_n, _stream())
+    return out, logprob, kept_n, kept_mass
+
+
 class HeadArgs(ctypes.Structure):
     """mirror of `quipamd_head_args`"""
     _fields_ = [("has_u", ctypes.c_int), ("U", Fop), ("u_y", ctypes.c_void_p), ("u_y_dtype", ctypes.c_int), ("u_bias", ctypes.c_void_p),
