@@ -73,6 +73,41 @@
 #define K2_WFIRST 1
 #endif
     constexpr bool WFIRST = EXACT && (K2_WFIRST != 0);
+    // K2_AHEAD (issue-ahead schedule): "request everything, then consume" keeps a wave in the ISSUE of its NCH * NDMA LDS-DMA instructions
+    // until the CU's vector-memory queue has drained that far (clock ~3900 of the headline launch, profiles/r06g_k2h_stamps_insitu.txt), and
+    // only then does it start its ~690 clocks per chunk of ds_read + dequant + MFMA: the four SIMDs idle through the ingest and do all their
+    // arithmetic behind it.  With AHEAD < NCH the prologue requests the weight tiles and the slabs of the first AHEAD chunks only; DMA
+    // instruction t of chunk i + AHEAD goes out in front of MFMA step t of chunk i (NI == NT: one instruction per step, 1 KiB of x against
+    // ~85 clocks of instructions; HALF: the even steps only).  Memory returns in order, so the counted wait in front of chunk i is "the
+    // slabs requested behind mine": chunks i + 1 .. min(i + AHEAD - 1, NCH - 1).  A slab is written once and never reused, so nothing guards
+    // a write after a read.  AHEAD = NCH is the old instruction stream exactly.  The arithmetic (MFMA order, the two chains, the meet) does
+    // not move: y is bit-identical for every AHEAD.  Measured: profiles/k2h_pipeline.md.
+    // Which instantiations: the headline <2, RT 1, 4 x 4> (HALF or not) of the one-problem kernel; every other one keeps AHEAD = NCH until an
+    // A/B on its own shape shows a gain.  -DK2_AHEAD=n (lab builds, scripts/k2lab.hip) forces n on EVERY exact instantiation.
+#ifdef K2_AHEAD
+    constexpr int AHEAD = WFIRST ? ((K2_AHEAD) < 1 ? 1 : (K2_AHEAD) > NCH ? NCH : (K2_AHEAD)) : NCH;
+#else
+    constexpr int AHEAD = (WFIRST && !K2_GROUPED && BITS == 2 && RT == 1 && NW == 4 && NCH == 4) ? 2 : NCH;
+#endif
+    static_assert(NI == NT, "one LDS-DMA instruction per MFMA step");
+    // K2_PIN: an empty asm that names accumulators ("a": they live in AGPRs; "v" cost 512 v_accvgpr copies) -- see `pin` in the MFMA loop.
+    // Device pass only: the host pass parses this body too, and "a" means something else there.
+#ifndef K2_PIN
+#if defined(__HIP_DEVICE_COMPILE__)
+#define K2_PIN(x) asm volatile("" : "+a"(x))
+#define K2_PIN2(x, y) asm volatile("" : "+a"(x), "+a"(y))
+#else
+#define K2_PIN(x) (void)(x)
+#define K2_PIN2(x, y) (void)(x), (void)(y)
+#endif
+#endif
+    // DMA instruction q of chunk i, for the requests between the MFMA steps.  (Its call in the chunk loop is compiled in the device pass only:
+    // the host pass, which parses this body too, takes the call inside the generic lambda as an error it never prints and then cannot form
+    // the kernel's address for qa_lds<> -- "cannot compile this l-value expression yet".)
+    auto dma = [&](int i, int q) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void2_t *)(myreg + i * XB + (q >> 1) * CBS + (q & 1) * 1024), 16, (q & 1) ? voff_hi : voff_lo,
+                                                 chunk_of(i) * ROWB + (q >> 1) * 128, 0, 0);
+    };
     u32x4 w[NCH][RT];
     if constexpr (WFIRST) {
 #pragma unroll
@@ -81,7 +116,7 @@
             for (int r = 0; r < RT; ++r) load_w_nt(w[i][r], A.qw + ((uint64_t)(rt0 + r) * nkc + chunk_of(i)) * 64 + lane);
     }
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
+    for (int i = 0; i < AHEAD; ++i) {
         const uint32_t kc = chunk_of(i);
         if (EXACT || kc < nkc) {                                      // wave-uniform
             if constexpr (!WFIRST) {
@@ -107,6 +142,14 @@
 #pragma unroll
     for (int r = 0; r < RT; ++r) acc[r][0] = acc[r][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const u32x4 ones = {opaque(ACT::ONES), opaque(ACT::ONES), opaque(ACT::ONES), opaque(ACT::ONES)};
+    // K2_PREFETCH (lab option): the eight ds_read_b128 of chunk i + 1 go out in front of the MFMA steps of chunk i, into the other of two fragment
+    // buffers (one wave per SIMD: registers to spare), so their LDS latency hides under arithmetic.  The counted wait for chunk i + 1's slab moves
+    // in front of chunk i's arithmetic with them.  Measured on top of K2_AHEAD: profiles/k2h_pipeline.md.
+#ifndef K2_PREFETCH
+#define K2_PREFETCH 0
+#endif
+    constexpr bool PREF = WFIRST && (K2_PREFETCH != 0) && AHEAD >= 2;     // chunk i + 1 must be in the queue while chunk i is consumed
+    u32x4 xfa[NT], xfb[NT];
     static_for<NCH>([&](auto I) {
         constexpr int i = decltype(I)::value;
         const uint32_t kc = chunk_of(i);
@@ -121,16 +164,29 @@
 #endif
             constexpr bool FINE = EXACT && (K2_FINE != 0) && i == NCH - 1 && NT == 2 * NCB;
             constexpr int OPL = WFIRST ? NDMA : OPC;                  // operations a LATER chunk has in the queue behind mine
-            constexpr int NWAIT = EXACT ? (NCH - 1 - i) * OPL + (FINE ? NDMA - (HALF ? 1 : 2) : 0) : 0;    // ragged K: everything, then compute
+            constexpr int LAST = i + AHEAD - 1 < NCH - 1 ? i + AHEAD - 1 : NCH - 1;    // the last chunk whose slab is in the queue behind mine
+            constexpr int NWAIT = EXACT ? (LAST - i) * OPL + (FINE ? NDMA - (HALF ? 1 : 2) : 0) : 0;    // ragged K: everything, then compute
+            constexpr int NXT = i + AHEAD;                            // the chunk whose slab is requested under this chunk's MFMA steps
+            constexpr int PWAIT = (LAST - i - 1) * OPL;              // PREF: chunk i + 1 has landed; chunk NXT is requested behind this wait
+            if constexpr (AHEAD < NCH && i > 0) {                     // the arithmetic of chunk i - 1 stays in front of this wait (see `pin` below)
+#pragma unroll
+                for (int r = 0; r < RT; ++r) K2_PIN2(acc[r][0], acc[r][1]);
+                K2_PIN2(accx[0], accx[1]);
+            }
+            if constexpr (i == 0 || !PREF) {
+            if constexpr (i < 4) K2_STAMP2(8 + i);
             if constexpr (RT == 1) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w[i][0]) : "n"(NWAIT) : "memory");
             else if constexpr (RT == 2) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w[i][0]), "+v"(w[i][1]) : "n"(NWAIT) : "memory");
             else {
                 static_assert(RT == 1 || RT == 2 || RT == 4, "row tiles per wave");
                 asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[i][0]), "+v"(w[i][1]), "+v"(w[i][2]), "+v"(w[i][RT - 1]) : "n"(NWAIT) : "memory");
             }
+            if constexpr (i < 4) K2_STAMP2(12 + i);
+            }
             if constexpr (i == 0) K2_STAMP(2);
             if constexpr (i == NCH - 1) K2_STAMP(3);
             if constexpr (FINE) {
+                static_assert(!PREF, "K2_FINE and K2_PREFETCH: one or the other");
                 static_for<NCB>([&](auto CB) {
                     constexpr int cb = decltype(CB)::value;
                     if constexpr (cb > 0) wait_vm<(NCH - 1 - i) * OPL + NDMA - (HALF ? 1 : 2) * (cb + 1)>();
@@ -146,14 +202,40 @@
                     }
                 });
             } else {
-            u32x4 xf[NT];
+            u32x4 xfl[NT];
+            u32x4 (&xf)[NT] = !PREF ? xfl : (i & 1) ? xfb : xfa;
+            if constexpr (i == 0 || !PREF) {
             static_for<NT>([&](auto T) {
                 constexpr int t = decltype(T)::value;
                 lds_read16<i * XB + (t >> 1) * CBS>(xf[t], (t & 1) ? rd1 : rd0);
             });
+            }
             wait_lgkm(xf);
+            if constexpr (PREF && i + 1 < NCH) {                      // the fragments of chunk i + 1, under this chunk's arithmetic
+                u32x4 (&xn)[NT] = (i & 1) ? xfa : xfb;
+                if constexpr (i + 1 < 4) K2_STAMP2(8 + i + 1);
+                if constexpr (RT == 1) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w[i + 1][0]) : "n"(PWAIT) : "memory");
+                else if constexpr (RT == 2) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w[i + 1][0]), "+v"(w[i + 1][1]) : "n"(PWAIT) : "memory");
+                else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[i + 1][0]), "+v"(w[i + 1][1]), "+v"(w[i + 1][2]), "+v"(w[i + 1][RT - 1]) : "n"(PWAIT) : "memory");
+                if constexpr (i + 1 < 4) K2_STAMP2(12 + i + 1);
+                static_for<NT>([&](auto T) {
+                    constexpr int t = decltype(T)::value;
+                    lds_read16<(i + 1) * XB + (t >> 1) * CBS>(xn[t], (t & 1) ? rd1 : rd0);
+                });
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
+                // pin (AHEAD < NCH only; no instruction): hipcc's scheduler moves MFMAs freely across the asm waits and the DMA requests -- it sank a
+                // whole chunk's arithmetic below the NEXT chunk's vmcnt wait and issued the eight requests in one clump.  An empty asm that names
+                // this step's accumulators sits behind MFMA step t - 2 and in front of step t, and keeps its place among the requests and waits.
+                if constexpr (AHEAD < NCH) {
+#pragma unroll
+                    for (int r = 0; r < RT; ++r) K2_PIN(acc[r][t & 1]);
+                    K2_PIN(accx[t & 1]);
+                }
+#if defined(__HIP_DEVICE_COMPILE__)
+                if (NXT < NCH && !((t & 1) && HALF)) dma(NXT, t);    // K2_AHEAD: one request per MFMA step
+#endif
 #pragma unroll
                 for (int r = 0; r < RT; ++r) acc[r][t & 1] = ACT::mfma(Q::frag(w[i][r], t), xf[t], acc[r][t & 1]);
                 accx[t & 1] = ACT::mfma(ones, xf[t], accx[t & 1]);   // row sums of x on the matrix pipe: D[.][b] = sum_k x[b,k]

@@ -22,6 +22,7 @@
 #include "probe.h"
 #ifndef K2_PROBE
 #define K2_STAMP(i) QA_STAMP(i)            /* nothing in the shipped library; the in-situ stamps of csrc/probe.h in the probe build */
+#define K2_STAMP2(i) QA_STAMP(i)           /* slots 8..15: in front of / behind the counted wait of chunk 0..3 (dq_h_body.inc) */
 #define K2_STAMP_FLUSH() do { } while (0)
 #define K2_ACC_DECL do { } while (0)
 #define K2_ACC(slot, stmt) stmt
@@ -107,6 +108,7 @@ struct K2Args {
 template <int BITS, class ACT, int RT, int NW, int NCH, bool HALF, bool EXACT>   // HALF: bs <= 8; EXACT: d / KC == NW * NCH
 __global__ __launch_bounds__(64 * NW) void dq_h_kernel(K2Args A)
 {
+    constexpr bool K2_GROUPED = false;
 #include "dq_h_body.inc"
 }
 
@@ -119,6 +121,7 @@ template <int BITS, class ACT, int RT, int NW, int NCH, bool HALF, bool EXACT>
 __global__ __launch_bounds__(64 * NW) void dq_hg_kernel(K2GArgs G)
 {
     const K2Args A = G.g[blockIdx.y];
+    constexpr bool K2_GROUPED = true;                                   // (the body's default schedule is decided per instantiation)
 #include "dq_h_body.inc"
 }
 

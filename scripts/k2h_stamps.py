@@ -8,7 +8,9 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ["QUIP_AMD_LIB"] = os.path.join(ROOT, "quip_amd", "csrc", "libquip_amd_probe.so")
+# QUIP_AMD_LIB, when set, names another probe build: `python __graft_entry__.py --variant probe_nch -DQA_PROBE -DK2_AHEAD=99` is the
+# "request everything, then consume" schedule next to the shipped one (profiles/k2h_pipeline.md)
+os.environ.setdefault("QUIP_AMD_LIB", os.path.join(ROOT, "quip_amd", "csrc", "libquip_amd_probe.so"))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -42,7 +44,7 @@ def run(m, d, bs, dt, launches=48, warm=False, cfg=None):
         st = buf.cpu().numpy().astype(np.int64).reshape(16, 16)
         live = st[:, 0] > 0
         t0 = st[live][:, 0].min()
-        rows.append(np.stack([np.where(st[live][:, k] > 0, st[live][:, k] - t0, -1) for k in range(8)], 1))
+        rows.append(np.stack([np.where(st[live][:, k] > 0, st[live][:, k] - t0, -1) for k in range(16)], 1))
     _lib.call("quipamd_probe_set", None)
     a = np.stack(rows)                                                   # [launch, wave, slot]
     print(f"\n{'kernel cfg ' + str(cfg) if cfg else 'default kernel'}: {m} x {d}, bs {bs}, {str(dt).split('.')[-1]}, {'WARM (one copy)' if warm else f'COLD (ring of {nring} copies)'}: {a.shape[1]} waves stamped in workgroup 5, "
@@ -52,6 +54,25 @@ def run(m, d, bs, dt, launches=48, warm=False, cfg=None):
         lo, hi = np.median(a[:, :, k].min(1)), np.median(a[:, :, k].max(1))
         print(f"  {k} {NAMES[k]:<52} {lo:7.0f} .. {hi:7.0f}   (+{hi - prev:6.0f} on the last wave; {hi / 2400:5.2f} us)")
         prev = hi
+    # slots 8 + i / 12 + i (dq_h_body.inc, chunks 0..3): in front of / behind the counted vmcnt wait of chunk i.  Per wave: the time STALLED in the
+    # wait, and the time in INSTRUCTIONS from that wait to the next one (ds_read, dequant, MFMA, the requests issued between the steps) --
+    # the two numbers the single "last chunk landed" stamp used to add up.
+    if (a[:, :, 8:16] > 0).any():
+        nxt = [9, 10, 11, 4]                                             # what follows chunk i's arithmetic: the next wait, or "last MFMA issued"
+        print("  chunk: wait reached at / stalled in the wait / instructions to the next wait -- median over launches of the per-launch "
+              "median wave (of the last wave)")
+        st_sum = in_sum = 0.0
+        for i in range(4):
+            if not (a[:, :, 12 + i] > 0).any():
+                continue
+            reach, stall, instr = a[:, :, 8 + i], a[:, :, 12 + i] - a[:, :, 8 + i], a[:, :, nxt[i]] - a[:, :, 12 + i]
+            last = a[:, :, 4].argmax(1)                                  # the wave that issues its last MFMA last
+            pick = lambda v: np.median(v[np.arange(len(last)), last])
+            print(f"    chunk {i}: {np.median(np.median(reach, 1)):7.0f} ({pick(reach):7.0f})   stalled {np.median(np.median(stall, 1)):6.0f} ({pick(stall):6.0f})"
+                  f"   instructions {np.median(np.median(instr, 1)):6.0f} ({pick(instr):6.0f})")
+            st_sum += pick(stall)
+            in_sum += pick(instr)
+        print(f"    last wave, chunks 0..3: {st_sum:.0f} clocks stalled in waits, {in_sum:.0f} in instructions")
 
 
 if __name__ == "__main__":

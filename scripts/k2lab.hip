@@ -8,6 +8,7 @@
 // probe build (-DK2_PROBE): per-wave s_memtime stamps (dq_h_kernel) and per-wave time spent in waits / barriers / issue (dq_s_kernel)
 __device__ unsigned long long *g_k2_probe = nullptr;
 #define K2_STAMP(i) do { if (g_k2_probe && (threadIdx.x & 63) == 0) g_k2_probe[((size_t)blockIdx.x * 32 + (threadIdx.x >> 6)) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
+#define K2_STAMP2(i) do { } while (0)      /* the in-situ split stamps of the library's probe build: this lab's buffer has 8 slots per wave */
 #define K2_STAMP_FLUSH() do { } while (0)
 #define K2_ACC_DECL unsigned long long k2_acc[4] = {0, 0, 0, 0}; const unsigned long long k2_t00 = __builtin_readcyclecounter()
 #define K2_ACC(slot, stmt) do { const unsigned long long t0_ = __builtin_readcyclecounter(); stmt; k2_acc[slot] += __builtin_readcyclecounter() - t0_; } while (0)
