@@ -1,4 +1,5 @@
-"""ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h, include/quip_amd_prefill.h and include/quip_amd_sample.h).
+"""ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h, include/quip_amd_prefill.h, include/quip_amd_sample.h and
+include/quip_amd_generate.h).
 
 The product path has no CPU fallback: if the shared library is missing or a symbol is absent, importing the
 ops fails loudly here.  Build it with `python __graft_entry__.py` (hipcc --offload-arch=gfx950).
@@ -111,6 +112,13 @@ SAMPLE_SIGNATURES = {
     "quipamd_sample_rows": [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
 }
 
+# the generation-control entry: include/quip_amd_generate.h, a fourth table for the same reason; tests/test_generate_host.py checks this table
+# against that header and tests/test_gpu_generate_contract.py runs every launching name of it under a guard arena
+GENERATE_SIGNATURES = {
+    "quipamd_generate_rows": [c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
+                              c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+}
+
 _lib = None
 
 
@@ -137,7 +145,7 @@ def load():
                                                                                                       "quipamd_dequant_gemm_grouped_config", "quipamd_decode_attention_config") else
                       c_i64 if name in ("quipamd_hessian_fast_workspace", "quipamd_vecquant_workspace_bytes", "quipamd_gptq_qfnb_workspace_bytes", "quipamd_gptq_qfnb_info_offset", "quipamd_preproc_workspace_bytes",
                                                           "quipamd_decode_attention_grouped_workspace_bytes", "quipamd_decode_attention_fused_max_len") else c_int)
-    for name, argtypes in list(PREFILL_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
+    for name, argtypes in list(PREFILL_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(GENERATE_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -521,7 +521,8 @@ def best_mode(dec, bs, dtype, max_len=None):
 class Sampling:
     """how DecodeEngine picks a token: temperature, top-k and top-p (Hugging Face's TopKLogitsWarper, then TopPLogitsWarper) and the 64-bit
     seed of the draws -- ops.sample_rows has the arithmetic.  temperature 0 or top_k 1 is greedy.  A plain value: validated here, compared by
-    value, no GPU involved.  Not served: EOS / stop handling, repetition penalties, per-sequence parameters, beam search."""
+    value, no GPU involved.  Stop tokens, the repetition penalty and per-sequence parameters are `Generation`'s.  Not served: min-length,
+    frequency / presence penalties, stop strings, beam search."""
     __slots__ = ("temperature", "top_k", "top_p", "seed")
 
     def __init__(self, temperature=1.0, top_k=0, top_p=1.0, seed=0):
@@ -557,12 +558,99 @@ class Sampling:
         return f"Sampling(temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p}, seed={self.seed})"
 
 
+class Generation:
+    """what ends and shapes a DecodeEngine continuation besides the draw itself -- ops.generate_rows has the arithmetic:
+      sampling            None (greedy), a `Sampling`, or a sequence of them, one per sequence of the batch
+      repetition_penalty  Hugging Face's RepetitionPenaltyLogitsProcessor over every token the sequence holds so far, prompt included:
+                          a finite number > 0 (1: off), or a sequence of them, one per sequence of the batch
+      stop_ids            at most 16 token ids; a sequence that draws one of them is finished: the stop token is its last, `pad_id` follows
+      pad_id              what a finished sequence yields (and is fed) from then on
+    A plain value like `Sampling`: validated here, compared by value, no GPU involved; per-sequence lengths are held against the engine's bs
+    by rows(bs).  Not served: min-length, frequency / presence penalties, stop strings, beam search."""
+    __slots__ = ("sampling", "repetition_penalty", "stop_ids", "pad_id")
+    MAX_STOP = ops.GENERATE_MAX_STOP
+
+    def __init__(self, sampling=None, repetition_penalty=1.0, stop_ids=(), pad_id=0):
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        is_seq = lambda v: isinstance(v, (list, tuple))
+        if is_seq(sampling):
+            sampling = tuple(sampling)
+            if not sampling or not all(isinstance(x, Sampling) for x in sampling):
+                raise ValueError("Generation: sampling must be None, a Sampling, or a non-empty sequence of Sampling (one per sequence)")
+        elif sampling is not None and not isinstance(sampling, Sampling):
+            raise ValueError(f"Generation: sampling must be None, a Sampling, or a sequence of Sampling (got {type(sampling).__name__})")
+
+        def penalty(v):
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                f = float("nan")
+            if isinstance(v, bool) or not 0.0 < f < float("inf"):
+                raise ValueError(f"Generation: repetition_penalty must be a finite number > 0 (1: off), got {v!r}")
+            return f
+        if is_seq(repetition_penalty):
+            if not repetition_penalty:
+                raise ValueError("Generation: repetition_penalty must be a number or a non-empty sequence of numbers (one per sequence)")
+            repetition_penalty = tuple(penalty(v) for v in repetition_penalty)
+        else:
+            repetition_penalty = penalty(repetition_penalty)
+        if isinstance(sampling, tuple) and isinstance(repetition_penalty, tuple) and len(sampling) != len(repetition_penalty):
+            raise ValueError(f"Generation: {len(sampling)} Sampling values but {len(repetition_penalty)} repetition penalties")
+        try:
+            stop_ids = tuple(stop_ids)
+        except TypeError:
+            raise ValueError(f"Generation: stop_ids must be a sequence of token ids (got {stop_ids!r})") from None
+        if len(stop_ids) > self.MAX_STOP:
+            raise ValueError(f"Generation: at most {self.MAX_STOP} stop ids (got {len(stop_ids)})")
+        if not all(is_int(v) and 0 <= v < 1 << 31 for v in stop_ids):
+            raise ValueError(f"Generation: stop_ids must be integers in [0, 2^31), got {stop_ids!r}")
+        if not is_int(pad_id) or not 0 <= pad_id < 1 << 31:
+            raise ValueError(f"Generation: pad_id must be an integer in [0, 2^31), got {pad_id!r}")
+        for name, v in zip(self.__slots__, (sampling, repetition_penalty, tuple(int(v) for v in stop_ids), int(pad_id))):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Generation is immutable: build a new one")
+
+    def rows(self, bs):
+        """[(temperature, top_k, top_p, seed, repetition_penalty)] for the bs sequences of an engine; ValueError when a per-sequence setting
+        is not bs long"""
+        for name in ("sampling", "repetition_penalty"):
+            v = getattr(self, name)
+            if isinstance(v, tuple) and len(v) != bs:
+                raise ValueError(f"Generation: {name} holds {len(v)} values, the engine runs {bs} sequences")
+        greedy = Sampling(temperature=0.0)
+        out = []
+        for b in range(bs):
+            s = self.sampling[b] if isinstance(self.sampling, tuple) else self.sampling or greedy
+            p = self.repetition_penalty[b] if isinstance(self.repetition_penalty, tuple) else self.repetition_penalty
+            out.append((s.temperature, s.top_k, s.top_p, s.seed, p))
+        return out
+
+    def _key(self):
+        return (self.sampling, self.repetition_penalty, self.stop_ids, self.pad_id)
+
+    def __eq__(self, other):
+        return isinstance(other, Generation) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"Generation(sampling={self.sampling!r}, repetition_penalty={self.repetition_penalty}, stop_ids={self.stop_ids}, "
+                f"pad_id={self.pad_id})")
+
+
 class DecodeEngine:
     """benchmark()'s per-token loop as ONE hipGraph replay per token: static KV cache [bs, kv_heads, max_len, hd] per block, position and
     current token on the device.  `forward(ids)` is `model(ids, past_key_values=...)` for the next position; `generate` is greedy unless a
     `Sampling` is set (set_sampling, or generate's `sampling=`): then every step ends with one sample launch (ops.sample_rows) instead of
     the argmax, replayed from a second graph.  The draw for the token fed at cache position t of sequence b is Philox(seed; t, b): the same
-    seed gives the same tokens with or without the graph, after prefill() or token-by-token feeding, and again after reset()."""
+    seed gives the same tokens with or without the graph, after prefill() or token-by-token feeding, and again after reset().
+    With a `Generation` set (set_generation, or generate's `generation=`) the launch that ends a step is ops.generate_rows instead: per-sequence
+    sampling parameters, a repetition penalty over `history`, stop tokens -- a third graph.  An engine that never sets one runs exactly the
+    launches and graphs it ran before Generation existed.  Not served: min-length, frequency / presence penalties, stop strings, beam search."""
+    poll = 8                 # generate() under a Generation reads `finished` every `poll` steps and stops once every sequence is done; 0: never
 
     def __init__(self, decoder, bs=1, max_len=2048, mode="auto", graph=True):
         self.dec = decoder
@@ -602,6 +690,12 @@ class DecodeEngine:
         self.logprob = torch.zeros(bs, dtype=torch.float32, device=self.dev)     # log-probability of the token of the last sampled step
         self.kept_n = torch.zeros(bs, dtype=torch.int32, device=self.dev)        # ... how many entries survived top-k / top-p in that step,
         self.kept_mass = torch.ones(bs, dtype=torch.float32, device=self.dev)    # ... and their share of the top-k mass
+        self._generation = None          # None: the steps above.  A Generation: every step ends with ops.generate_rows (_one_generation)
+        self._generation_written = None  # what the device parameters hold
+        self._gen_params = self._stop_ids = None     # ops.generate_params(bs) and int32 [16] stop ids (-1: unused), made by the first set_generation
+        self._graphs_generation = {}     # pad_id -> graph (pad_id is an argument of the launch; everything else is read from the device)
+        self.history = self.finished = self.stop_pos = None      # int32 [bs, max_len + 1] (-1: not recorded), int32 [bs], int64 [bs] (-1: none)
+        self.lengths = None              # after generate() under a Generation: int64 [bs] on the host, tokens up to and including the stop token
 
     @classmethod
     def from_hf(cls, model, packed=None, bs=1, max_len=2048, mode="auto", graph=True, device=None):
@@ -641,6 +735,53 @@ class DecodeEngine:
         ops.sample_rows(self.logits, self._sample_params, self.pos, out=self.ids, logprob=self.logprob, kept_n=self.kept_n, kept_mass=self.kept_mass,
                         clear=self.part_idx if self._fh else None)
 
+    @property
+    def generation(self):
+        return self._generation
+
+    def set_generation(self, generation):
+        """None: the engine as it is without generation control (greedy, or the `Sampling` in force).  A `Generation`: every following step,
+        and the end of prefill(), ends with ops.generate_rows.  The first call allocates `history`, `finished` and `stop_pos`; parameters and
+        stop ids live on the device and are read by the launch at run time, so changing them rewrites them (two small copies) and never
+        recaptures a graph (a new pad_id, an argument of the launch, captures a graph of its own on its first step).  `finished` and
+        `stop_pos` are cleared by reset(), not here; `history` records the tokens fed while a Generation is in force.  With stop ids set,
+        feed a prompt through prefill(): forward() ends every fed token with a launch, whose token may finish the sequence."""
+        if generation is not None and not isinstance(generation, Generation):
+            raise TypeError(f"DecodeEngine.set_generation: a decode.Generation or None (got {type(generation).__name__})")
+        if generation is not None and generation != self._generation_written:
+            rows = generation.rows(self.bs)                                   # raises before anything is written
+            stops = list(generation.stop_ids) + [-1] * (Generation.MAX_STOP - len(generation.stop_ids))
+            if self._gen_params is None:
+                self._gen_params = ops.generate_params(self.bs, device=self.dev)
+                self._stop_ids = torch.full((Generation.MAX_STOP,), -1, dtype=torch.int32, device=self.dev)
+                self.history = torch.full((self.bs, self.max_len + 1), -1, dtype=torch.int32, device=self.dev)
+                self.finished = torch.zeros(self.bs, dtype=torch.int32, device=self.dev)
+                self.stop_pos = torch.full((self.bs,), -1, dtype=torch.int64, device=self.dev)
+            ops.write_generate_params(self._gen_params, None, *[[r[i] for r in rows] for i in range(5)])
+            self._stop_ids.copy_(torch.tensor(stops, dtype=torch.int32))
+            self._generation_written = generation
+        self._generation = generation
+
+    def _generate_launch(self, fed):
+        """the launch that ends a step under a Generation; counter = the device position, as in _sample().  fed: the token just fed at
+        position counter - 1 (`ids`, which the launch then overwrites), or None when the caller wrote `history` itself (prefill)"""
+        ops.generate_rows(self.logits, self._gen_params, self.pos, hist=self.history, fed=fed, stop_ids=self._stop_ids,
+                          pad_id=self._generation.pad_id, done=self.finished, stop_pos=self.stop_pos, out=self.ids, logprob=self.logprob,
+                          kept_n=self.kept_n, kept_mass=self.kept_mass, clear=self.part_idx if self._fh else None)
+
+    def _one_generation(self):
+        """_one_sampled()'s launch sequence with ops.generate_rows in place of the sample launch, for greedy rows too"""
+        if self.attn_workspace is not None:
+            self.dec.attn_workspace = self.attn_workspace
+        if self._fh:
+            self.dec.step_fused_head(self.ids, self.pos, self.caches, self.logits, self.part_val, self.part_idx)
+            self._generate_launch(self.ids)
+            return
+        lg = self.dec.step(self.ids, self.pos, self.caches, self.arange)
+        self.logits.copy_(lg)
+        self.pos.add_(1)
+        self._generate_launch(self.ids)
+
     def _one_sampled(self):
         if self.attn_workspace is not None:
             self.dec.attn_workspace = self.attn_workspace
@@ -654,6 +795,8 @@ class DecodeEngine:
         self._sample()
 
     def _one(self):
+        if self._generation is not None:
+            return self._one_generation()
         if self._sampling is not None:
             return self._one_sampled()
         if self.attn_workspace is not None:              # (a decoder may serve several engines: each step brings its own)
@@ -671,9 +814,15 @@ class DecodeEngine:
         self._steps = 0
         if self._fh:
             self.part_idx.fill_(-1)
+        if self.history is not None:
+            self.history.fill_(-1)
+            self.finished.zero_()
+            self.stop_pos.fill_(-1)
 
     def _state(self):
         ts = [self.pos, self.ids, self.logits, self.logprob]
+        if self._generation is not None:                 # ... and what a generate launch at the current position writes besides
+            ts += [self.finished, self.stop_pos, self.history[:, self._steps:self._steps + 2]]
         return ts + [self.part_val, self.part_idx] if self._fh else ts
 
     @torch.no_grad()
@@ -703,6 +852,10 @@ class DecodeEngine:
     @torch.no_grad()
     def _prepare(self):
         if not self._want_graph:
+            return
+        if self._generation is not None:                 # a third launch sequence: its own graph, captured on first use like the sampled one
+            if self._generation.pad_id not in self._graphs_generation:
+                self._graphs_generation[self._generation.pad_id] = self._capture_in_place()
             return
         if self._sampling is not None:                   # the sampled step is a launch sequence of its own: a second graph, captured on first use
             if self._graph_sampled is None:
@@ -735,7 +888,10 @@ class DecodeEngine:
         if self._steps >= self.max_len:
             raise RuntimeError("DecodeEngine: KV cache full (max_len %d)" % self.max_len)
         self._prepare()
-        g = self._graph if self._sampling is None else self._graph_sampled
+        if self._generation is not None:
+            g = self._graphs_generation.get(self._generation.pad_id)
+        else:
+            g = self._graph if self._sampling is None else self._graph_sampled
         if g is not None:
             g.replay()
         else:
@@ -805,7 +961,10 @@ class DecodeEngine:
                 outs.append(lg)
         last = lg[:, -1] if all_logits else lg
         self.logits.copy_(last)
-        if self._sampling is None:
+        if self._generation is not None:                 # the prompt is the history so far; nothing was "just fed" for the launch to record
+            self.history[:, self._steps:self._steps + n].copy_(ids)
+            self._generate_launch(None)
+        elif self._sampling is None:
             ops.argmax_rows(self.logits, out=self.ids)
         else:
             self._sample()                               # pos is behind the prompt by now: the position the drawn token is fed at
@@ -842,11 +1001,24 @@ class DecodeEngine:
         return float(torch.exp(torch.stack(nlls).sum() / (nsamples * seqlen)))
 
     @torch.no_grad()
-    def generate(self, first, n, sampling=None):
+    def generate(self, first, n, sampling=None, generation=None):
         """continuation: returns int64 [n, bs] -- the n tokens following `first`.  Greedy (model.generate(do_sample=False) with a cache) unless
         a `Sampling` is in force: the engine's (set_sampling), or `sampling`, which applies to this call only -- the previous setting is put
-        back afterwards, also when the call raises.
-        `first`: one token per sequence (int or [bs]), or a prompt [bs, n_prompt], which is prefilled in one pass."""
+        back afterwards, also when the call raises.  `generation` does the same for a `Generation` (not both in one call).
+        `first`: one token per sequence (int or [bs]), or a prompt [bs, n_prompt], which is prefilled in one pass.
+        Under a Generation the result is int64 [n', bs]: a sequence that drew a stop token holds `pad_id` behind it, stepping ends once every
+        sequence is finished (the host reads `finished` every `poll` steps -- the one synchronisation this adds), and the result is cut to
+        n' = the latest stop's step + 1 whatever `poll` is (n' == n when some sequence never stopped).  `lengths` then holds, per sequence,
+        the number of tokens up to and including its stop token (n' if it never stopped)."""
+        if sampling is not None and (generation is not None or self._generation is not None):
+            raise ValueError("DecodeEngine.generate: sampling= and a Generation exclude each other -- pass generation=Generation(sampling=...)")
+        if generation is not None:
+            prev = self._generation
+            self.set_generation(generation)
+            try:
+                return self.generate(first, n)
+            finally:
+                self.set_generation(prev)
         if sampling is not None:
             prev = self._sampling
             self.set_sampling(sampling)
@@ -858,6 +1030,8 @@ class DecodeEngine:
             self.prefill(first)
         else:
             self.forward(first)
+        if self._generation is not None:
+            return self._generate_controlled(n)
         out = []
         for i in range(n):
             if self._fh and self._sampling is None:      # the embed launch of step i + 1 writes step i's argmax into `ids`
@@ -871,6 +1045,25 @@ class DecodeEngine:
                 if i < n - 1:
                     self.step()
         return torch.stack(out)
+
+    def _generate_controlled(self, n):
+        """generate()'s loop under a Generation: token i of the result is the one fed at position c0 + i, so a stop recorded at position
+        stop_pos is step stop_pos - c0"""
+        c0 = self._steps
+        out = []
+        for i in range(n):
+            out.append(self.ids.clone())
+            if i == n - 1:
+                break
+            if self.poll and (i + 1) % self.poll == 0 and bool(self.finished.all()):
+                break
+            self.step()
+        toks = torch.stack(out) if out else torch.empty((0, self.bs), dtype=torch.int64, device=self.dev)
+        done, at = self.finished.cpu(), self.stop_pos.cpu() - c0             # (rows finished before this call: a step below 0)
+        stopped = (done != 0) & (at < len(out))
+        n_out = int(at[stopped].max().clamp_(min=-1)) + 1 if bool(stopped.all()) and self.bs else len(out)
+        self.lengths = torch.where(stopped, (at + 1).clamp_(min=0), torch.full_like(at, n_out))
+        return toks[:n_out]
 
     @torch.no_grad()
     def benchmark(self, input_ids, check=False, verbose=False):

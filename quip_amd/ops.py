@@ -1371,6 +1371,105 @@ def sample_rows(logits, params, counter, out=None, logprob=None, kept_n=None, ke
     return out, logprob, kept_n, kept_mass
 
 
+class GenerateParams(ctypes.Structure):
+    """mirror of `quipamd_generate_params` (include/quip_amd_generate.h): one per row"""
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("top_k", ctypes.c_int32), ("repetition_penalty", ctypes.c_float),
+                ("seed", ctypes.c_uint64)]
+
+
+GENERATE_PARAMS_BYTES = ctypes.sizeof(GenerateParams)     # 24
+GENERATE_MAX_STOP = 16
+
+
+def _generate_params_host(temperature, top_k, top_p, seed, repetition_penalty):
+    gp = GenerateParams(float(temperature), float(top_p), max(-1, min(int(top_k), 0x7fffffff)), float(repetition_penalty), int(seed) & 0xffffffffffffffff)
+    return bytes(gp)
+
+
+def generate_params(rows, device=None):
+    """a uint8 [rows, 24] device tensor holding `quipamd_generate_params[rows]`, every row at the defaults of write_generate_params"""
+    t = torch.empty((rows, GENERATE_PARAMS_BYTES), dtype=torch.uint8, device=device)
+    return write_generate_params(t)
+
+
+def write_generate_params(t, r=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, repetition_penalty=1.0):
+    """rewrite row r of the `quipamd_generate_params[rows]` held by t (uint8 [rows, 24] on the device) in place -- r None: every row.  Each
+    of the five values is a number, or with r None a sequence of `rows` of them.  One small host-to-device copy on the current stream;
+    the generate launch reads the structs at run time, so a captured graph that holds the launch follows the change."""
+    _need_gpu(t)
+    assert t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] == GENERATE_PARAMS_BYTES and t.is_contiguous() and t.data_ptr() % 8 == 0
+    rows = t.shape[0]
+    vals = (temperature, top_k, top_p, seed, repetition_penalty)
+    if r is not None:
+        assert 0 <= int(r) < rows
+        t[int(r)].copy_(torch.frombuffer(bytearray(_generate_params_host(*vals)), dtype=torch.uint8))
+        return t
+    per_row = []
+    for v in vals:
+        if isinstance(v, (list, tuple)):
+            assert len(v) == rows, f"write_generate_params: a sequence of {len(v)} values for {rows} rows"
+            per_row.append(list(v))
+        else:
+            per_row.append([v] * rows)
+    raw = b"".join(_generate_params_host(*row) for row in zip(*per_row))
+    if rows:
+        t.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8).view(rows, GENERATE_PARAMS_BYTES))
+    return t
+
+
+def generate_rows(logits, params, counter, hist=None, fed=None, stop_ids=None, pad_id=0, done=None, stop_pos=None, out=None, logprob=None,
+                  kept_n=None, kept_mass=None, clear=None):
+    """sample_rows with per-row parameters, a repetition penalty and stop tokens, one launch (quipamd_generate_rows,
+    include/quip_amd_generate.h has the contract).  params: generate_params(rows); counter: int64 [1] on the device, c below.
+      hist      int32 [rows, cap] (row stride >= cap): the kernel stores hist[r, c - 1] = fed[r] (fed: int64 [rows], may be `out`), penalises
+                the logits of the distinct ids in hist[r, :min(c, cap)] -- x < 0 ? x * p : x / p, on the fly: `logits` keeps its bits --
+                and stores hist[r, c] = out[r]; positions outside [0, cap) are skipped
+      stop_ids  int32 [<= 16] on the device; done int32 [rows], stop_pos int64 [rows]: a row with done != 0 yields pad_id (logprob 0,
+                kept_n 0, kept_mass 1) without reading its logits; a row that draws a stop id gets done = 1, stop_pos = c
+    Each of hist / fed / stop_ids / done / stop_pos may be None, which switches that part off.  Returns (out, logprob, kept_n, kept_mass)."""
+    _need_gpu(logits, params, counter, hist, fed, stop_ids, done, stop_pos, out, logprob, kept_n, kept_mass, clear)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    rows, n = logits.shape
+    assert (params.dtype == torch.uint8 and params.dim() == 2 and tuple(params.shape) == (rows, GENERATE_PARAMS_BYTES) and params.is_contiguous()
+            and params.data_ptr() % 8 == 0)
+    assert counter.dtype == torch.int64 and counter.numel() == 1
+    hist_cap = ld_hist = 0
+    if hist is not None:
+        assert hist.dtype == torch.int32 and hist.dim() == 2 and hist.shape[0] == rows and hist.shape[1] >= 1 and hist.stride(1) == 1
+        hist_cap = hist.shape[1]
+        ld_hist = hist.stride(0) if rows > 1 else max(hist_cap, hist.stride(0))
+        assert ld_hist >= hist_cap
+    if fed is not None:
+        assert fed.dtype == torch.int64 and fed.numel() == rows and fed.is_contiguous()
+    n_stop = 0
+    if stop_ids is not None:
+        assert stop_ids.dtype == torch.int32 and stop_ids.dim() == 1 and stop_ids.numel() <= GENERATE_MAX_STOP and stop_ids.is_contiguous()
+        n_stop = stop_ids.numel()
+    assert 0 <= int(pad_id) < 1 << 31
+    if done is not None:
+        assert done.dtype == torch.int32 and done.numel() == rows and done.is_contiguous()
+    if stop_pos is not None:
+        assert stop_pos.dtype == torch.int64 and stop_pos.numel() == rows and stop_pos.is_contiguous()
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    if logprob is None:
+        logprob = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if kept_n is None:
+        kept_n = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    if kept_mass is None:
+        kept_mass = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    for t, dt in ((out, torch.int64), (logprob, torch.float32), (kept_n, torch.int32), (kept_mass, torch.float32)):
+        assert t.dtype == dt and t.numel() == rows and t.is_contiguous()
+    clear_n = 0
+    if clear is not None:
+        assert clear.dtype == torch.int32 and clear.dim() == 2 and clear.shape[0] == rows and clear.is_contiguous()
+        clear_n = clear.shape[1]
+    _lib.call("quipamd_generate_rows", _p(logits), _dtype(logits), rows, n, logits.stride(0) if rows > 1 else max(n, logits.stride(0)),
+              _p(params), _p(counter), _p(hist), hist_cap, ld_hist, _p(fed), _p(stop_ids if n_stop else None), n_stop, int(pad_id), _p(done),
+              _p(stop_pos), _p(out), _p(logprob), _p(kept_n), _p(kept_mass), _p(clear), clear_n, _stream())
+    return out, logprob, kept_n, kept_mass
+
+
 class HeadArgs(ctypes.Structure):
     """mirror of `quipamd_head_args`"""
     _fields_ = [("has_u", ctypes.c_int), ("U", Fop), ("u_y", ctypes.c_void_p), ("u_y_dtype", ctypes.c_int), ("u_bias", ctypes.c_void_p),
