@@ -15,10 +15,10 @@
     static_assert(RT * 1024 + 64 <= NCH * XB, "a wave parks its partials in its own slab region");
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [NW][NCH] slabs; a wave parks its partials in its own
     const EpiArgs &e = A.e;
-    // (round 3, negative result, scripts/k2_ab.sh on one box, alternating runs: fetching every kernarg field in ONE scalar round trip
-    //  up front -- the fix that took 2000 cycles off the prologue of csrc/decode_fused.hip -- makes THIS kernel 0.13 us slower, 5.13 vs
-    //  4.98 us at K = 20 and 4.92 vs 4.79 at K = 2000: its lazily fetched fields already let the weight loads go out after the first
-    //  two s_loads, and waiting for all fifteen delays them)
+    // (round 3, negative result, scripts/k2_ab.sh on one box, alternating runs: WAITING for all fifteen kernarg fields in one scalar round
+    //  trip up front -- the fix that took 2000 cycles off the prologue of csrc/decode_fused.hip -- made this kernel 0.13 us slower than the
+    //  lazily fetched head it had then.  The head is now K2_HEAD below: the weight requests need qw and d only, which arrive preloaded in the
+    //  one-problem kernel and in one round trip in the grouped one; nothing waits for the other fields in front of the tiles.)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     K2_STAMP(0);
@@ -26,24 +26,6 @@
     const int j = lane & 15, g = lane >> 4;
     const uint32_t nkc = (uint32_t)(A.d / KC);
     const uint32_t rt0 = blockIdx.x * RT;
-    const uint32_t rowbytes = (uint32_t)A.d * 2u;
-    char *myreg = smem + wave * (NCH * XB);
-
-    // reducer role u = 4*r2 + q (below); the epilogue parameters of this wave's first role are requested now
-    float e_sc = 0.f, e_zr = 0.f, e_bi = 0.f;
-    if (wave < 4 * RT) {
-        const int64_t row = (int64_t)(rt0 + (wave >> 2)) * 16 + (lane & 15);
-        e_sc = e.qfn == QUIPAMD_QFN_B ? e.scale[0] : e.scale[row];
-        if (e.qfn != QUIPAMD_QFN_B) e_zr = e.zero[row];
-        if (e.bias) e_bi = e.bias[row];
-    }
-
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)A.x, 0, (int)(e.bs * (int64_t)rowbytes), 0x00020000);
-    const uint32_t voff_lo = (lane >> 3) * rowbytes + ((uint32_t)((lane & 7) ^ (lane >> 3)) << 4);
-    const uint32_t voff_hi = voff_lo + 8u * rowbytes;
-    const uint32_t rd_base = lds_addr(myreg) + (HALF ? 0 : (j >> 3) * 1024) + (j & 7) * 128;
-    const uint32_t rd0 = rd_base + (((0 + g) ^ (j & 7)) << 4);        // even MFMA steps
-    const uint32_t rd1 = rd_base + (((4 + g) ^ (j & 7)) << 4);        // odd MFMA steps
 
     // Which k-chunks a wave owns (round 5).  Rounds 2-4: wave w owns chunks w, w + NW, ... in every workgroup.  scripts/xingest_lab.hip
     // (profiles/r05d / r05e_xingest_lab.txt) timed the ingest of x alone -- 128 KiB into every CU of a 256-workgroup launch: 4091-4790
@@ -101,6 +83,71 @@
 #define K2_PIN2(x, y) (void)(x), (void)(y)
 #endif
 #endif
+    // ---- the head of the wave (K2_HEAD, profiles/k2h_head.md) ---------------------------------------------------------------------------
+    // The cold critical path is wave start -> kernel arguments -> weight request -> HBM round trip -> chunk 0 -> ... -> store: whatever sits in
+    // front of the weight request delays the whole launch by as much.  So the weight tiles are the wave's FIRST vector-memory instructions and
+    // only what their addresses need (qw, d) is read in front of them.  The epilogue parameters (first used behind the meet) are requested
+    // between the weight tiles and the first x slab: still in front of every slab, so no counted wait changes -- the waits count the
+    // operations behind a chunk's slab.  K2_HEAD_PIN: hipcc's scheduler moves scalar arithmetic (and the s_waitcnt lgkmcnt its operands need)
+    // freely across the asm loads; the two fields the code right behind the weight tiles reads (qfn: which epilogue loads; bs: the extent of
+    // x's descriptor) pass through an empty asm, and volatile asms keep their order.  The "memory" clobbers keep the epilogue loads between
+    // the weight tiles and the LDS-DMA builtins.  -DK2_HEAD=0 (lab builds): the old order -- epilogue parameters, then the weight tiles.
+#ifndef K2_HEAD
+#define K2_HEAD 1
+#endif
+#ifndef K2_HEAD_PIN
+#if defined(__HIP_DEVICE_COMPILE__)
+#define K2_HEAD_PIN(q, b) asm volatile("" : "+s"(q), "+s"(b) : : "memory")
+#define K2_HEAD_FENCE() asm volatile("" : : : "memory")
+#define K2_HEAD_ARG(p) asm volatile("" : "+s"(p))
+#else
+#define K2_HEAD_ARG(p) (void)(p)
+#define K2_HEAD_PIN(q, b) (void)(q), (void)(b)
+#define K2_HEAD_FENCE() (void)0
+#endif
+#endif
+    int h_qfn = e.qfn;
+    int64_t h_bs = e.bs;
+    // reducer role u = 4*r2 + q (below): the epilogue parameters of this wave's first role
+    float e_sc = 0.f, e_zr = 0.f, e_bi = 0.f;
+    auto request_epi = [&]() {
+        if (wave < 4 * RT) {
+            const int64_t row = (int64_t)(rt0 + (wave >> 2)) * 16 + (lane & 15);
+            e_sc = h_qfn == QUIPAMD_QFN_B ? e.scale[0] : e.scale[row];
+            if (h_qfn != QUIPAMD_QFN_B) e_zr = e.zero[row];
+            if (e.bias) e_bi = e.bias[row];
+        }
+        K2_HEAD_FENCE();
+    };
+    if constexpr (K2_HEAD == 0) request_epi();
+    u32x4 w[NCH][RT];
+    K2_STAMP2(12);                                                    // in front of the first weight request
+    if constexpr (WFIRST) {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i)
+#pragma unroll
+            for (int r = 0; r < RT; ++r) load_w_nt(w[i][r], A.qw + ((uint64_t)(rt0 + r) * nkc + chunk_of(i)) * 64 + lane);
+    } else if constexpr (K2_HEAD != 0) {                              // chunk by chunk: the first chunk's tiles (the loop below skips them)
+        const u32x4 *qw0 = A.qw;
+        K2_HEAD_ARG(qw0);                                             // read with d, in ONE round trip: not inside the branch, behind d
+        if (EXACT || chunk_of(0) < nkc) {
+#pragma unroll
+            for (int r = 0; r < RT; ++r) load_w_nt(w[0][r], qw0 + ((uint64_t)(rt0 + r) * nkc + chunk_of(0)) * 64 + lane);
+        }
+    }
+    if constexpr (K2_HEAD != 0) {
+        K2_HEAD_PIN(h_qfn, h_bs);
+        request_epi();
+    }
+
+    const uint32_t rowbytes = (uint32_t)A.d * 2u;
+    char *myreg = smem + wave * (NCH * XB);
+    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)A.x, 0, (int)(h_bs * (int64_t)rowbytes), 0x00020000);
+    const uint32_t voff_lo = (lane >> 3) * rowbytes + ((uint32_t)((lane & 7) ^ (lane >> 3)) << 4);
+    const uint32_t voff_hi = voff_lo + 8u * rowbytes;
+    const uint32_t rd_base = lds_addr(myreg) + (HALF ? 0 : (j >> 3) * 1024) + (j & 7) * 128;
+    const uint32_t rd0 = rd_base + (((0 + g) ^ (j & 7)) << 4);        // even MFMA steps
+    const uint32_t rd1 = rd_base + (((4 + g) ^ (j & 7)) << 4);        // odd MFMA steps
     // DMA instruction q of chunk i, for the requests between the MFMA steps.  (Its call in the chunk loop is compiled in the device pass only:
     // the host pass, which parses this body too, takes the call inside the generic lambda as an error it never prints and then cannot form
     // the kernel's address for qa_lds<> -- "cannot compile this l-value expression yet".)
@@ -108,20 +155,15 @@
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void2_t *)(myreg + i * XB + (q >> 1) * CBS + (q & 1) * 1024), 16, (q & 1) ? voff_hi : voff_lo,
                                                  chunk_of(i) * ROWB + (q >> 1) * 128, 0, 0);
     };
-    u32x4 w[NCH][RT];
-    if constexpr (WFIRST) {
-#pragma unroll
-        for (int i = 0; i < NCH; ++i)
-#pragma unroll
-            for (int r = 0; r < RT; ++r) load_w_nt(w[i][r], A.qw + ((uint64_t)(rt0 + r) * nkc + chunk_of(i)) * 64 + lane);
-    }
 #pragma unroll
     for (int i = 0; i < AHEAD; ++i) {
         const uint32_t kc = chunk_of(i);
         if (EXACT || kc < nkc) {                                      // wave-uniform
             if constexpr (!WFIRST) {
+            if (K2_HEAD == 0 || i > 0) {
 #pragma unroll
             for (int r = 0; r < RT; ++r) load_w_nt(w[i][r], A.qw + ((uint64_t)(rt0 + r) * nkc + kc) * 64 + lane);
+            }
             }
 #pragma unroll
             for (int q = 0; q < NI; ++q) {
@@ -129,10 +171,9 @@
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_void2_t *)(myreg + i * XB + (q >> 1) * CBS + (q & 1) * 1024), 16, (q & 1) ? voff_hi : voff_lo,
                                                          kc * ROWB + (q >> 1) * 128, 0, 0);
             }
-        } else {
-#pragma unroll
-            for (int r = 0; r < RT; ++r) w[i][r] = u32x4{0u, 0u, 0u, 0u};
         }
+        // (a chunk past the end of a ragged K: its w[i] is never read, the chunk loop skips it.  It used to be zeroed here; that join of an asm
+        //  load with a constant is a copy hipcc may place BEFORE the load's data has landed -- tests/test_k2_isa.py caught it once the head moved)
     }
 
     K2_STAMP(1);
@@ -181,7 +222,7 @@
                 static_assert(RT == 1 || RT == 2 || RT == 4, "row tiles per wave");
                 asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[i][0]), "+v"(w[i][1]), "+v"(w[i][2]), "+v"(w[i][RT - 1]) : "n"(NWAIT) : "memory");
             }
-            if constexpr (i < 4) K2_STAMP2(12 + i);
+            if constexpr (i > 0 && i < 4) K2_STAMP2(12 + i);  // (chunk 0: slot 2, right below; slot 12 is the head's)
             }
             if constexpr (i == 0) K2_STAMP(2);
             if constexpr (i == NCH - 1) K2_STAMP(3);
@@ -269,11 +310,26 @@
         const int b = 4 * q + (lane >> 4), wr = lane & 15;
         const int src = r2 * 256 + (wr & 3) * 64 + b + 16 * (wr >> 2);
         float a = 0.f, xsum = 0.f;
+        // K2_TAIL: hipcc read the row sums, waited lgkmcnt(0), and only then issued the reads of the partials -- two LDS latencies in series on
+        // the tail of every launch.  All 2 NW reads go out, the scheduler may move nothing across the barrier, and the sums (in the same order:
+        // the arithmetic does not move) wait behind it.  -DK2_TAIL=0 (lab builds): no barrier -- hipcc's own order, as measured before.
+#ifndef K2_TAIL
+#define K2_TAIL 1
+#endif
+        float pa[NW], px[NW];
 #pragma unroll
         for (int v = 0; v < NW; ++v) {
             const float *p = reinterpret_cast<const float *>(smem + v * (NCH * XB));
-            a += p[src];
-            xsum += p[RT * 256 + b];
+            pa[v] = p[src];
+            px[v] = p[RT * 256 + b];
+        }
+#if K2_TAIL && defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+            a += pa[v];
+            xsum += px[v];
         }
         const int64_t row = (int64_t)(rt0 + r2) * 16 + wr;
         if (b < e.bs) {

@@ -22,7 +22,7 @@
 #include "probe.h"
 #ifndef K2_PROBE
 #define K2_STAMP(i) QA_STAMP(i)            /* nothing in the shipped library; the in-situ stamps of csrc/probe.h in the probe build */
-#define K2_STAMP2(i) QA_STAMP(i)           /* slots 8..15: in front of / behind the counted wait of chunk 0..3 (dq_h_body.inc) */
+#define K2_STAMP2(i) QA_STAMP(i)           /* slots 8..15: in front of / behind the counted wait of chunk 0..3; 12: in front of the first weight request (dq_h_body.inc) */
 #define K2_STAMP_FLUSH() do { } while (0)
 #define K2_ACC_DECL do { } while (0)
 #define K2_ACC(slot, stmt) stmt
@@ -105,9 +105,46 @@ struct K2Args {
 // The weight tiles are asm loads (form (ii) of cdna_hip_programming.md 5.7): straight-line code, consumed right
 // behind the wait that names them; tests/test_k2_isa.py audits the generated code for touches in between.
 // =====================================================================================================================
+// Arguments (K2_FLAT_ARGS, profiles/k2h_head.md): a FLAT list, the pointers the head of the wave needs first.  gfx950's dispatcher can deliver
+// the first kernel arguments in SGPRs before the wave starts (the kernel descriptor's kernarg_preload_length), which takes the read of a
+// cold argument block off the front of the weight request -- but hipcc (ROCm 7.2) preloads scalar arguments only: a by-value struct gets
+// length 0.  With -mllvm -amdgpu-kernarg-preload-count=16 (the build's per-source flags) x .. y below arrive in 14 SGPRs; the rest is read
+// as before.  The body is compiled unchanged from a local K2Args.  -DK2_FLAT_ARGS=0 (lab builds): the struct signature.
+#ifndef K2_FLAT_ARGS
+#define K2_FLAT_ARGS 1
+#endif
+#if K2_FLAT_ARGS
+// The pointers travel as 64-bit integers and the scalars behind them as ONE struct: eight arguments, none of pointer type.  Measured
+// (profiles/k2h_head.md, section 5): as fifteen arguments, six of them typed pointers, hipLaunchKernel alone took 4.03 us against 3.71 for
+// the parent's single struct, and an un-queued eager loop ran at the host's pace (4.61 us per launch against 4.42); in this form the host
+// cost is 3.73 and the loop 4.15.  Not the dispatcher's preload fetch: the same signature without the preload flag runs that loop at 4.33.
+struct K2HTail {
+    int qfn, maxq, y_f32, y_f16, accumulate;
+    float two_over_maxq;
+    int64_t bs, m;
+};
+#define K2_H_PARAMS uint64_t x_, uint64_t qw_, int64_t d, uint64_t scale_, uint64_t zero_, uint64_t bias_, uint64_t y_, K2HTail t
+#define K2_H_PASS(A) (uint64_t)(uintptr_t)(A).x, (uint64_t)(uintptr_t)(A).qw, (A).d, (uint64_t)(uintptr_t)(A).e.scale, (uint64_t)(uintptr_t)(A).e.zero, \
+                     (uint64_t)(uintptr_t)(A).e.bias, (uint64_t)(uintptr_t)(A).e.y, \
+                     K2HTail{(A).e.qfn, (A).e.maxq, (A).e.y_f32, (A).e.y_f16, (A).e.accumulate, (A).e.two_over_maxq, (A).e.bs, (A).e.m}
+#else
+#define K2_H_PARAMS K2Args A
+#define K2_H_PASS(A) (A)
+#endif
 template <int BITS, class ACT, int RT, int NW, int NCH, bool HALF, bool EXACT>   // HALF: bs <= 8; EXACT: d / KC == NW * NCH
-__global__ __launch_bounds__(64 * NW) void dq_h_kernel(K2Args A)
+__global__ __launch_bounds__(64 * NW) void dq_h_kernel(K2_H_PARAMS)
 {
+#if K2_FLAT_ARGS
+    K2Args A;
+    // (through address space 1: an integer cast straight to a generic pointer would turn every access into a flat one)
+#define K2_GLOBAL(T, v) ((T *)(__attribute__((address_space(1))) T *)(v))
+    A.x = K2_GLOBAL(const uint16_t, x_); A.qw = K2_GLOBAL(const u32x4, qw_); A.d = d;
+    A.e.scale = K2_GLOBAL(const float, scale_); A.e.zero = K2_GLOBAL(const float, zero_); A.e.bias = K2_GLOBAL(const float, bias_);
+    A.e.y = K2_GLOBAL(void, y_);
+#undef K2_GLOBAL
+    A.e.qfn = t.qfn; A.e.maxq = t.maxq; A.e.y_f32 = t.y_f32; A.e.y_f16 = t.y_f16; A.e.accumulate = t.accumulate;
+    A.e.two_over_maxq = t.two_over_maxq; A.e.bs = t.bs; A.e.m = t.m;
+#endif
     constexpr bool K2_GROUPED = false;
 #include "dq_h_body.inc"
 }
@@ -241,7 +278,7 @@ int launch_h2(const K2Args &A, hipStream_t s)
     static_assert(lds <= QA_LDS_MAX, "LDS budget");
     constexpr auto kern = dq_h_kernel<BITS, ACT, RT, NW, NCH, HALF, EXACT>;
     if (int rc = qa_lds<kern>(lds, "dequant_gemm")) return rc;
-    kern<<<dim3((unsigned)(A.e.m / 16 / RT)), 64 * NW, lds, s>>>(A);
+    kern<<<dim3((unsigned)(A.e.m / 16 / RT)), 64 * NW, lds, s>>>(K2_H_PASS(A));
     QA_LAUNCH_CHECK("quipamd_dequant_gemm(h)");
     return QUIPAMD_OK;
 }

@@ -54,7 +54,13 @@ def run(m, d, bs, dt, launches=48, warm=False, cfg=None):
         lo, hi = np.median(a[:, :, k].min(1)), np.median(a[:, :, k].max(1))
         print(f"  {k} {NAMES[k]:<52} {lo:7.0f} .. {hi:7.0f}   (+{hi - prev:6.0f} on the last wave; {hi / 2400:5.2f} us)")
         prev = hi
-    # slots 8 + i / 12 + i (dq_h_body.inc, chunks 0..3): in front of / behind the counted vmcnt wait of chunk i.  Per wave: the time STALLED in the
+    # slot 12 (dq_h_body.inc): immediately in front of the first weight request -- the head of the launch: what a wave spends between its
+    # start and the request whose HBM round trip everything else waits for (profiles/k2h_head.md)
+    if (a[:, :, 12] > 0).any():
+        hd = a[:, :, 12] - a[:, :, 0]                                    # per wave: its own start -> its own first weight request
+        print(f"  head: own start -> first weight request, per wave: median {np.median(hd):6.0f}, first wave {np.median(hd.min(1)):6.0f}, "
+              f"last wave {np.median(hd.max(1)):6.0f}; first weight request of the last wave at {np.median(a[:, :, 12].max(1)):6.0f}")
+    # slots 8 + i / 12 + i (dq_h_body.inc, chunks 0..3; behind chunk 0's wait: slot 2, which sits right behind it): in front of / behind the counted vmcnt wait of chunk i.  Per wave: the time STALLED in the
     # wait, and the time in INSTRUCTIONS from that wait to the next one (ds_read, dequant, MFMA, the requests issued between the steps) --
     # the two numbers the single "last chunk landed" stamp used to add up.
     if (a[:, :, 8:16] > 0).any():
@@ -63,9 +69,10 @@ def run(m, d, bs, dt, launches=48, warm=False, cfg=None):
               "median wave (of the last wave)")
         st_sum = in_sum = 0.0
         for i in range(4):
-            if not (a[:, :, 12 + i] > 0).any():
+            behind = 2 if i == 0 else 12 + i
+            if not (a[:, :, behind] > 0).any():
                 continue
-            reach, stall, instr = a[:, :, 8 + i], a[:, :, 12 + i] - a[:, :, 8 + i], a[:, :, nxt[i]] - a[:, :, 12 + i]
+            reach, stall, instr = a[:, :, 8 + i], a[:, :, behind] - a[:, :, 8 + i], a[:, :, nxt[i]] - a[:, :, behind]
             last = a[:, :, 4].argmax(1)                                  # the wave that issues its last MFMA last
             pick = lambda v: np.median(v[np.arange(len(last)), last])
             print(f"    chunk {i}: {np.median(np.median(reach, 1)):7.0f} ({pick(reach):7.0f})   stalled {np.median(np.median(stall, 1)):6.0f} ({pick(stall):6.0f})"
@@ -76,6 +83,10 @@ def run(m, d, bs, dt, launches=48, warm=False, cfg=None):
 
 
 if __name__ == "__main__":
+    if "--headline" in sys.argv:                                     # the headline launch alone, cold and warm
+        run(4096, 4096, 16, torch.bfloat16, cfg=(2, 4, 4))
+        run(4096, 4096, 16, torch.bfloat16, warm=True, cfg=(2, 4, 4))
+        sys.exit(0)
     run(4096, 4096, 16, torch.bfloat16, cfg=(2, 4, 4))               # dq_h_kernel 4 x 4: x through LDS-DMA slabs
     run(4096, 4096, 16, torch.bfloat16, warm=True, cfg=(2, 4, 4))
     run(4096, 4096, 16, torch.bfloat16, cfg=(2, 44, 4))              # dq_hr_kernel: x straight into registers (round 6)

@@ -1,6 +1,9 @@
 // k2lab.hip -- standalone lab for the K2 kernels (not part of the library): correctness against a host fp64 reference of
 // the reference formula (quant.py:13-14, 222-233) and per-launch time inside a hipGraph, cold (weight ring > 256 MiB) and warm.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I include -I quip_amd/csrc scripts/k2lab.hip -o build/k2lab
+//        + the flags build() gives csrc/dqgemm_v2.hip (`python -c "import __graft_entry__ as g; print(*g.hip_flags('dqgemm_v2.hip'))"`: today
+//        -mllvm -amdgpu-kernarg-preload-count=16) -- without them dq_h_kernel is NOT the shipped kernel: preload length 0, its arguments read in
+//        a scalar round trip in front of the weight tiles (launch_h passes them through K2_H_PASS either way: csrc/dqgemm_v2.h)
 // run:   build/k2lab <mode> [m d bs bits act]     mode: null | h | s | mb | old
 #include "../quip_amd/csrc/capi.hip"
 #include "../quip_amd/csrc/dqgemm.hip"
