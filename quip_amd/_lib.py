@@ -1,5 +1,5 @@
-"""ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h, include/quip_amd_prefill.h, include/quip_amd_sample.h and
-include/quip_amd_generate.h).
+"""ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h, include/quip_amd_prefill.h, include/quip_amd_sample.h,
+include/quip_amd_generate.h and include/quip_amd_score.h).
 
 The product path has no CPU fallback: if the shared library is missing or a symbol is absent, importing the
 ops fails loudly here.  Build it with `python __graft_entry__.py` (hipcc --offload-arch=gfx950).
@@ -119,6 +119,13 @@ GENERATE_SIGNATURES = {
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
 }
 
+# the scoring entries: include/quip_amd_score.h, a fifth table for the same reason; tests/test_score_host.py checks this table against that
+# header and tests/test_gpu_score_contract.py runs every launching name of it under a guard arena
+SCORE_SIGNATURES = {
+    "quipamd_head_score_workspace_bytes": [c_i64, c_i64],
+    "quipamd_head_score": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+}
+
 _lib = None
 
 
@@ -152,6 +159,13 @@ def load():
             raise QuipAmdError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes
         fn.restype = c_int
+    for name, argtypes in SCORE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise QuipAmdError(f"{LIB_PATH} does not export {name}; rebuild it") from e
+        fn.argtypes = argtypes
+        fn.restype = c_i64 if name.endswith("_workspace_bytes") else c_int
     _lib = lib
     return lib
 

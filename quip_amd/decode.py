@@ -21,6 +21,7 @@ packed or still dense) and picks the fastest launch sequence the layers allow:
     plain    layer.forward() per Linear (also dense nn.Linear models: the fp16 baseline of the same harness)
 
 There is no CPU path: the engine raises on a model that is not on a GPU."""
+import collections
 import time
 
 import numpy as np
@@ -240,14 +241,17 @@ class OPTDecoder(nn.Module):
             prev = blk.fc2
         return prev, y2, x
 
-    def prefill(self, ids, pos, caches, arange, all_logits=False):
+    def prefill(self, ids, pos, caches, arange, all_logits=False, hidden=False):
         """ids int64 [bs, T] at cache positions pos .. pos + T - 1 (pos int64 [1] on the device, not advanced here); returns the logits of
-        the last position [bs, vocab], or of every position [bs, T, vocab]"""
+        the last position [bs, vocab], or of every position [bs, T, vocab]; hidden=True: no head -- the final LayerNorm's output of every
+        position [bs * T, h], what the head multiplies (DecodeEngine.score hands it to ops.head_score)"""
         bs, T = ids.shape
         x = self.tok(ids) + F.embedding(arange[:T] + pos + 2, self.posemb.weight)        # learned positions start + t + 2
         x = x.reshape(bs * T, self.h)
         for blk, (kc, vc) in zip(self.blocks, caches):
             x = blk.prefill(x, kc, vc, pos, T)
+        if hidden:
+            return self.lnf(x)
         if all_logits:
             return self.head(x).view(bs, T, -1)
         return self.head(x.view(bs, T, self.h)[:, -1])
@@ -437,13 +441,16 @@ class LlamaDecoder(nn.Module):
             prev = blk.down_proj
         return prev, yd, x
 
-    def prefill(self, ids, pos, caches, arange, all_logits=False):
+    def prefill(self, ids, pos, caches, arange, all_logits=False, hidden=False):
         """ids int64 [bs, T] at cache positions pos .. pos + T - 1 (pos int64 [1] on the device, not advanced here); returns the logits of
-        the last position [bs, vocab], or of every position [bs, T, vocab]"""
+        the last position [bs, vocab], or of every position [bs, T, vocab]; hidden=True: no head -- the final RMSNorm's output of every
+        position [bs * T, h], what the head multiplies (DecodeEngine.score hands it to ops.head_score)"""
         bs, T = ids.shape
         x = self.tok(ids).reshape(bs * T, self.h)
         for blk, (kc, vc) in zip(self.blocks, caches):
             x = blk.prefill(x, kc, vc, pos, T, self.cos, self.sin)
+        if hidden:
+            return self.norm(x)
         if all_logits:
             return self.head(x).view(bs, T, -1)
         return self.head(x.view(bs, T, self.h)[:, -1])
@@ -925,6 +932,27 @@ class DecodeEngine:
         rows = self.PREFILL_BYTES // (self._ffn_width() * item * self.bs)
         return max(64, rows // 64 * 64)
 
+    def _refuse_prompt(self, who, what, prompt_ids, chunk):
+        """the refusals of a prompt pass (prefill, score), raised before anything is written; returns (n, chunk)"""
+        if not torch.is_tensor(prompt_ids) or prompt_ids.dim() != 2 or prompt_ids.shape[0] != self.bs or prompt_ids.shape[1] < 1:
+            shape = tuple(prompt_ids.shape) if torch.is_tensor(prompt_ids) else type(prompt_ids).__name__
+            raise ValueError(f"DecodeEngine.{who}: {what} must be int64 [bs = {self.bs}, n >= 1] (got {shape})")
+        n = prompt_ids.shape[1]
+        if self._steps + n > self.max_len:
+            raise RuntimeError(f"DecodeEngine.{who}: a prompt of {n} positions does not fit the KV cache ({self._steps} of max_len "
+                               f"{self.max_len} positions are in use)")
+        for name, m in self.dec.named_modules():
+            if isinstance(m, QuantLinear) and m.qweight.numel() == 0 and m.infeatures * m.outfeatures:
+                raise RuntimeError(f"DecodeEngine.{who}: layer {name} went through QuantLinear.decode_only(): it kept the decode-order codes "
+                                   "only, and the prompt pass runs the layers' forward on the natural-order codes.  Build the engine from the "
+                                   "packed checkpoint without decode_only() (or re-pack the layer), or feed the prompt token by token with forward()")
+        if chunk is None:
+            chunk = self.prefill_chunk()
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"DecodeEngine.{who}: chunk must be at least 1")
+        return n, chunk
+
     @torch.no_grad()
     def prefill(self, prompt_ids, chunk=None, all_logits=False):
         """feed a whole prompt, int64 [bs, n] with n >= 1, in passes of at most `chunk` positions per sequence (default: prefill_chunk()):
@@ -933,23 +961,7 @@ class DecodeEngine:
         already holds positions the prompt continues the sequence.  Returns `logits` [bs, vocab], or with all_logits the logits of every
         prompt position [bs, n, vocab].  Raises before anything is written when the prompt does not fit the cache, bs is wrong, or a layer
         dropped its natural-order codes (QuantLinear.decode_only)."""
-        if not torch.is_tensor(prompt_ids) or prompt_ids.dim() != 2 or prompt_ids.shape[0] != self.bs or prompt_ids.shape[1] < 1:
-            shape = tuple(prompt_ids.shape) if torch.is_tensor(prompt_ids) else type(prompt_ids).__name__
-            raise ValueError(f"DecodeEngine.prefill: prompt_ids must be int64 [bs = {self.bs}, n >= 1] (got {shape})")
-        n = prompt_ids.shape[1]
-        if self._steps + n > self.max_len:
-            raise RuntimeError(f"DecodeEngine.prefill: a prompt of {n} positions does not fit the KV cache ({self._steps} of max_len "
-                               f"{self.max_len} positions are in use)")
-        for name, m in self.dec.named_modules():
-            if isinstance(m, QuantLinear) and m.qweight.numel() == 0 and m.infeatures * m.outfeatures:
-                raise RuntimeError(f"DecodeEngine.prefill: layer {name} went through QuantLinear.decode_only(): it kept the decode-order codes "
-                                   "only, and the prompt pass runs the layers' forward on the natural-order codes.  Build the engine from the "
-                                   "packed checkpoint without decode_only() (or re-pack the layer), or feed the prompt token by token with forward()")
-        if chunk is None:
-            chunk = self.prefill_chunk()
-        chunk = int(chunk)
-        if chunk < 1:
-            raise ValueError("DecodeEngine.prefill: chunk must be at least 1")
+        n, chunk = self._refuse_prompt("prefill", "prompt_ids", prompt_ids, chunk)
         self._prepare()                                  # (its warm-up and capture steps write position 0 and reset: before the first cache write)
         ids = prompt_ids.to(device=self.dev, dtype=torch.int64)
         outs = []
@@ -976,10 +988,79 @@ class DecodeEngine:
         return self.logits
 
     @torch.no_grad()
-    def perplexity(self, input_ids):
+    def score(self, ids, targets=None, chunk=None, vocab=None):
+        """feed ids int64 [bs, n] from the engine's current position like prefill() -- same passes of `chunk` positions, same defaults, same
+        refusals before anything is written, same cache rows, the engine advances by n -- but end every pass in ops.head_score on its
+        hidden states instead of the head: no [rows, vocab] tensor is built and no logit is rounded to 16 bits.  Returns (logprob fp32
+        [bs, n], greedy int64 [bs, n]): the log-probability of targets[b, t] given ids[b, :t + 1] and the arg-max token of that position.
+        targets int64 [bs, n], default the next token (targets[:, t] = ids[:, t + 1], the last position -1); a negative target is an ignored
+        position (logprob 0), one at or past the vocabulary gives -inf.  vocab: score against the first `vocab` rows of the head only (the
+        reference scores [:, :, :50272] of OPT's padded table).  `logits` and `ids` are left as they were: to generate afterwards, feed a
+        token (forward)."""
+        n, chunk = self._refuse_prompt("score", "ids", ids, chunk)
+        W = self.dec.head_weight
+        vocab = W.shape[0] if vocab is None else int(vocab)
+        if not 1 <= vocab <= W.shape[0]:
+            raise ValueError(f"DecodeEngine.score: vocab {vocab} outside the head's {W.shape[0]} rows")
+        if targets is not None and (not torch.is_tensor(targets) or tuple(targets.shape) != (self.bs, n)):
+            shape = tuple(targets.shape) if torch.is_tensor(targets) else type(targets).__name__
+            raise ValueError(f"DecodeEngine.score: targets must be int64 [bs = {self.bs}, n = {n}] (got {shape})")
+        self._prepare()
+        ids = ids.to(device=self.dev, dtype=torch.int64)
+        if targets is None:
+            targets = torch.cat([ids[:, 1:], torch.full((self.bs, 1), -1, dtype=torch.int64, device=self.dev)], dim=1)
+        else:
+            targets = targets.to(device=self.dev, dtype=torch.int64)
+        rows = self.bs * min(chunk, n)
+        ws = self.__dict__.get("_score_ws")                  # one workspace per engine: sized for the head's whole table, grown only by a larger pass
+        if ws is None or ws[0] < rows:
+            ws = (rows, ops.head_score_workspace(rows, W.shape[0], self.dev))
+            self.__dict__["_score_ws"] = ws
+        logprob = torch.empty((self.bs, n), dtype=torch.float32, device=self.dev)
+        greedy = torch.empty((self.bs, n), dtype=torch.int64, device=self.dev)
+        for lo in range(0, n, chunk):
+            part = ids[:, lo:lo + chunk]
+            T = part.shape[1]
+            x = self.dec.prefill(part, self.pos, self.caches, self.arange, hidden=True)          # [bs * T, h], row b * T + t
+            self.pos.add_(T)
+            lp, _, gr = ops.head_score(x, W, targets[:, lo:lo + T].reshape(-1), vocab=vocab, workspace=ws[1])
+            logprob[:, lo:lo + T] = lp.view(self.bs, T)
+            greedy[:, lo:lo + T] = gr.view(self.bs, T)
+        if self._generation is not None:                     # the fed tokens are history, as after prefill(); nothing is drawn here
+            self.history[:, self._steps:self._steps + n].copy_(ids)
+        if self._fh:
+            self.part_idx.fill_(-1)                          # the next step's embed launch reads `ids`, not the partials of an earlier step
+        self._steps += n
+        return logprob, greedy
+
+    @torch.no_grad()
+    def loglikelihood(self, requests, vocab=None):
+        """the reference's zero-shot scoring (zeroShot BaseLM._loglikelihood_tokens): requests is a sequence of (context_ids,
+        continuation_ids), both non-empty lists of ints; returns [(sum of the continuation's log-probabilities given the context,
+        would greedy decoding have produced the continuation)] in request order.  Batching is collate_requests(requests, bs, max_len):
+        longest first, bs at a time, inputs cut from the left to max_len, right-padded with token 0 (causal attention keeps the pad out
+        of the positions before it), a short last batch filled with copies of its first request.  Every batch is one score() from an empty
+        cache and one device-to-host copy; the engine is at position 0 afterwards.  A continuation longer than max_len raises ValueError
+        before any GPU work.  vocab: as in score()."""
+        batches = collate_requests(requests, self.bs, self.max_len)
+        out = [None] * len(requests)
+        for b in batches:
+            self.reset()
+            tg = b.targets.to(self.dev)
+            lp, gr = self.score(b.ids.to(self.dev), tg, vocab=vocab)
+            hit = ((gr == tg) | (tg < 0)).all(dim=1)
+            both = torch.stack([lp.double().sum(dim=1), hit.double()], dim=1).cpu()               # targets < 0 contribute exactly 0
+            for r in range(b.real):
+                out[b.index[r]] = (float(both[r, 0]), bool(both[r, 1] != 0))
+        self.reset()
+        return out
+
+    @torch.no_grad()
+    def perplexity(self, input_ids, fused=False):
         """the reference's evaluation (opt.py:287-297, llama.py:244-250) on the engine's own layers: input_ids int64 [nsamples, seqlen], every
         sample an independent sequence prefilled from an empty cache (bs samples per pass); shifted cross-entropy in fp32,
-        exp(sum nll / (nsamples * seqlen)) with nll = mean CE of the sample * seqlen.  Returns a float."""
+        exp(sum nll / (nsamples * seqlen)) with nll = mean CE of the sample * seqlen.  Returns a float.
+        fused=True: the mean NLL comes from score() -- fp32 logits inside the head kernel, no [bs, seqlen, vocab] tensor."""
         input_ids = input_ids.to(self.dev)
         if input_ids.dim() != 2 or input_ids.shape[1] < 2:
             raise ValueError("DecodeEngine.perplexity: input_ids must be [nsamples, seqlen >= 2]")
@@ -993,6 +1074,11 @@ class DecodeEngine:
             if real < self.bs:                           # the last pass: pad with copies of its first sample, which are not counted
                 batch = torch.cat([batch, batch[:1].expand(self.bs - real, seqlen)])
             self.reset()
+            if fused:
+                lp, _ = self.score(batch)                # next-token targets; the last position is ignored (0)
+                for r in range(real):
+                    nlls.append((-lp[r, :-1].double().sum() / (seqlen - 1)).float() * seqlen)
+                continue
             lg = self.prefill(batch, all_logits=True)
             for r in range(real):
                 loss = F.cross_entropy(lg[r, :-1].float(), batch[r, 1:])
@@ -1106,10 +1192,10 @@ def benchmark(model, input_ids, check=False, engine=None):
     return res
 
 
-def perplexity(model, testenc, engine=None):
+def perplexity(model, testenc, engine=None, fused=False):
     """the reference's `opt_eval` / `llama_eval` figure (opt.py:194-297, llama.py:175-251) on the decode engine built over `model` (kept on
     the model between calls): testenc is the tokenised test set ([1, N] ids, or the tokenizer's output with .input_ids), cut into
-    N // model.seqlen samples of model.seqlen tokens; prints and returns the perplexity"""
+    N // model.seqlen samples of model.seqlen tokens; prints and returns the perplexity.  fused: DecodeEngine.perplexity's flag"""
     ids = getattr(testenc, "input_ids", testenc)
     seqlen = int(model.seqlen)
     nsamples = ids.numel() // seqlen
@@ -1119,6 +1205,55 @@ def perplexity(model, testenc, engine=None):
         eng = DecodeEngine.from_hf(model, max_len=seqlen)
         model.__dict__["_quip_decode_engine"] = eng
     print('Evaluating ...')
-    ppl = eng.perplexity(ids)
+    ppl = eng.perplexity(ids, fused=True) if fused else eng.perplexity(ids)
     print(ppl)
     return ppl
+
+
+ScoreBatch = collections.namedtuple("ScoreBatch", "ids targets index real")
+
+
+def collate_requests(requests, bs, max_len):
+    """the batching of the reference's zero-shot scoring, as a pure function (no GPU): requests is a sequence of (context_ids,
+    continuation_ids), both non-empty lists of ints.  The requests are ordered by (-len(ctx + cont), tuple(ctx + cont)) and taken bs at a
+    time; a request's input is (ctx + cont)[-(max_len + 1):][:-1], right-padded with token 0 to the batch's first (longest) input; its
+    targets are the continuation on the last len(cont) input positions and -1 everywhere else (the pad included).  A short last batch is
+    filled with copies of its first request.  Returns [ScoreBatch(ids int64 [bs, n], targets int64 [bs, n], index: the request index of
+    every row, real: how many leading rows are requests of their own)].  ValueError for an empty context or continuation and for a
+    continuation longer than max_len."""
+    reqs = []
+    for i, (ctx, cont) in enumerate(requests):
+        ctx, cont = [int(t) for t in ctx], [int(t) for t in cont]
+        if not ctx or not cont:
+            raise ValueError(f"collate_requests: request {i} has an empty context or continuation")
+        if len(cont) > max_len:
+            raise ValueError(f"collate_requests: the continuation of request {i} has {len(cont)} tokens, more than max_len {max_len}")
+        reqs.append((i, ctx + cont, cont))
+    reqs.sort(key=lambda r: (-len(r[1]), tuple(r[1])))
+    batches = []
+    for lo in range(0, len(reqs), bs):
+        group = reqs[lo:lo + bs]
+        real = len(group)
+        group = group + [group[0]] * (bs - real)
+        inputs = [toks[-(max_len + 1):][:-1] for _, toks, _ in group]
+        n = len(inputs[0])
+        ids = torch.zeros((bs, n), dtype=torch.int64)
+        targets = torch.full((bs, n), -1, dtype=torch.int64)
+        for r, (inp, (_, _, cont)) in enumerate(zip(inputs, group)):
+            ids[r, :len(inp)] = torch.tensor(inp, dtype=torch.int64)
+            targets[r, len(inp) - len(cont):len(inp)] = torch.tensor(cont, dtype=torch.int64)
+        batches.append(ScoreBatch(ids, targets, [g[0] for g in group], real))
+    return batches
+
+
+def loglikelihood(model, requests, engine=None, bs=1):
+    """the reference's zero-shot scoring (zeroShot BaseLM._loglikelihood_tokens) on the decode engine built over `model` (kept on the
+    model between calls, like perplexity): requests is a sequence of (context_ids, continuation_ids) token lists -- no tokenizer is
+    needed --; returns [(log-likelihood of the continuation, is it the greedy continuation)] in request order.  The context window is
+    model.seqlen when set, else the model's max_position_embeddings."""
+    eng = engine or getattr(model, "_quip_decode_engine", None)
+    if eng is None or (engine is None and eng.bs != bs):
+        max_len = int(getattr(model, "seqlen", 0) or model.config.max_position_embeddings)
+        eng = DecodeEngine.from_hf(model, bs=bs, max_len=max_len)
+        model.__dict__["_quip_decode_engine"] = eng
+    return eng.loglikelihood(requests)

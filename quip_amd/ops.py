@@ -1,4 +1,4 @@
-"""Thin torch-tensor wrappers over the C ABI (include/quip_amd.h).
+"""Thin torch-tensor wrappers over the C ABI (include/quip_amd.h and its sibling headers).
 
 torch is used for device memory and the current HIP stream only; every op below launches a hand-written
 gfx950 kernel from libquip_amd.so.  Inputs must live on a GPU -- there is no CPU fallback (a CPU tensor
@@ -1264,6 +1264,44 @@ def prefill_attention(q, k, v, kcache, vcache, start, T, cos_table=None, sin_tab
     _lib.call("quipamd_prefill_attention", _p(q), _p(k), _p(v), _p(kcache), _p(vcache), _p(start), T, _p(out), _p(cos_table), _p(sin_table),
               rows, _dtype(q), bs, heads, kv_heads, hd, maxlen, ctypes.c_float(sc), ld(q), ld(k), ld(v), _stream())
     return out
+
+
+def head_score_workspace(rows, vocab, device):
+    """the workspace quipamd_head_score needs for `rows` rows against `vocab` entries (the per-slice partials; no initialisation, nothing
+    is carried between calls): one workspace serves any number of calls of at most this size that run one after another on a stream"""
+    n = int(_lib.load().quipamd_head_score_workspace_bytes(int(rows), int(vocab)))
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
+
+
+def head_score(x, W, targets, vocab=None, out=None, workspace=None):
+    """the lm_head GEMM with a log-probability epilogue, two launches (quip_amd/csrc/head_score.hip, include/quip_amd_score.h): with
+    z = x W[:vocab]^T kept in fp32, returns (logprob, lse, greedy): lse[r] = logsumexp z[r], greedy[r] = the first arg-max of z[r] (int64),
+    logprob[r] = z[r, t] - lse[r] for t = targets[r] in [0, vocab), 0 for t < 0 (an ignored position), -inf for t >= vocab.  The
+    [rows, vocab] logits are never written.
+    x: [rows, h] f16/bf16, row stride a multiple of 8; W: [>= vocab, h] of the same type (vocab defaults to all its rows); targets: int64
+    [rows] on the device; h % 32 == 0.  out: (logprob fp32 [rows], lse fp32 [rows], greedy int64 [rows]) to write into; workspace:
+    head_score_workspace(rows, vocab, device), allocated here when None.  Runs are bit-identical, and a row's outputs do not depend on the
+    other rows of the call."""
+    _need_gpu(x, W, targets, workspace, *(out or ()))
+    assert x.dim() == 2 and W.dim() == 2 and x.shape[1] == W.shape[1] and x.dtype == W.dtype
+    assert x.stride(1) == 1 and W.stride(1) == 1
+    rows, h = x.shape
+    vocab = W.shape[0] if vocab is None else int(vocab)
+    assert 1 <= vocab <= W.shape[0], f"vocab {vocab} outside the table's {W.shape[0]} rows"
+    assert targets.dtype == torch.int64 and targets.numel() == rows and targets.is_contiguous()
+    ld = lambda t: t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.float32, device=x.device), torch.empty(rows, dtype=torch.float32, device=x.device),
+               torch.empty(rows, dtype=torch.int64, device=x.device))
+    logprob, lse, greedy = out
+    assert logprob.dtype == lse.dtype == torch.float32 and greedy.dtype == torch.int64
+    assert all(t.numel() == rows and t.is_contiguous() for t in out)
+    if workspace is None:
+        workspace = head_score_workspace(rows, vocab, x.device)
+    assert workspace.is_contiguous()
+    _lib.call("quipamd_head_score", _p(x), ld(x), _p(W), ld(W), _p(targets), _dtype(x), rows, h, vocab, _p(logprob), _p(lse), _p(greedy),
+              _p(workspace), workspace.numel() * workspace.element_size(), _stream())
+    return logprob, lse, greedy
 
 
 @functools.lru_cache(maxsize=None)
