@@ -100,6 +100,8 @@ template <int BITS, class ACT> struct DeqT {
     }
 };
 // ---- "multi-exponent" dequantisation (2-bit codes): 10 VALU per packed dword instead of 16 --------------------------------
+// Used by the streaming kernels (dq_s / dq_sg), dq_mb_kernel, the decode launches and, since profiles/k2h_me.md, the 4 waves x 4 chunks forms
+// of the one-pass kernel (dq_h_body.inc) and dq_hr_kernel.
 // The VALU port issues one instruction per 4 cycles per SIMD, and at bs <= 16 nothing amortises the dequantisation: it is
 // THE bound of the streaming kernel (profiles/r02e_k2_pmc_summary.txt: 4.4 M VALU instructions per launch at 28672 x 7168 =
 // 8.2 us of issue slots, as long as the HBM stream itself).  A 2-bit field can sit on ANY mantissa position p whose unit

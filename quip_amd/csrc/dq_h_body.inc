@@ -2,7 +2,19 @@
 // grouped one `dq_hg_kernel(K2GArgs G)` (blockIdx.y picks the problem): the SAME text compiled twice, so that the headline kernel's
 // generated code does not move when the grouped form is built (tests/test_k2_isa.py audits both).  Expects `A` (K2Args) in scope and the
 // template parameters BITS, ACT, RT, NW, NCH, HALF, EXACT.
-    typedef DeqT<BITS, ACT> Q;
+    // The dequantiser.  Multi-exponent (dq_common.h, DeqME2: 10 VALU per packed dword instead of 16) for the 2-bit forms of 4 waves x 4 chunks --
+    // d = 4096: the headline, its half-slab twin, RT 2 / 4, ragged K, the grouped kernel.  There a wave runs one chain of 32 MFMA steps, one wave
+    // per SIMD, and the chunk interval is its own instruction stream (profiles/k2h_pipeline.md section 4, profiles/k2h_me.md).  The offset of a
+    // dequantised value then depends on k, so the meet needs S_off = sum_k OFF_k x beside S_1 = sum_k x: both come from the ONE row-sum MFMA of
+    // a step (`sfr` below).  Every other form keeps the uniform offset: with 8 or 16 steps per wave the constants and the two fragments cost
+    // more instructions than the shifts they save (8 x 1: 311 against 268 in all), and the fp32 sums carry offsets of 128 / 64 instead of 4
+    // (1e-5 instead of 1e-6 relative on y), which the last-bit comparisons of the d = 2048 forms with the fused operator kernel
+    // (tests/test_gpu_method.py) do not allow.  -DK2_H_UNIFORM=1 (lab builds, scripts/k2lab.hip; default in dqgemm_v2.h): uniform everywhere.
+#if K2_H_UNIFORM
+    typedef DeqUni<BITS, ACT> Q;
+#else
+    typedef typename std::conditional<NW == 4 && NCH == 4, DeqSel<BITS, ACT>, DeqUni<BITS, ACT>>::type Q;
+#endif
     constexpr int KC = Q::KC, NT = Q::NT;
     // HALF (bs <= 8): a slab holds rows 0..7 only -- 1 KiB per 128-byte column block instead of 2 -- and lanes j >= 8 read the rows of j - 8
     // (their batch columns are never stored).  Half the LDS: d = 8192 (32 chunks) fits a workgroup at bs <= 8 (round 6: OPT's fc2 in a blocked
@@ -12,7 +24,7 @@
     //  return path beside the ~28 B/clk/CU LDS-DMA path, made the launch 0.9 us SLOWER)
     constexpr int NDMA = HALF ? NI / 2 : NI, OPC = RT + NDMA;         // vector-memory operations per chunk
     static_assert((NCH - 1) * OPC < 64, "vmcnt range");
-    static_assert(RT * 1024 + 64 <= NCH * XB, "a wave parks its partials in its own slab region");
+    static_assert(RT * 1024 + 128 <= NCH * XB, "a wave parks its partials and its two row sums in its own slab region");
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [NW][NCH] slabs; a wave parks its partials in its own
     const EpiArgs &e = A.e;
     // (round 3, negative result, scripts/k2_ab.sh on one box, alternating runs: WAITING for all fifteen kernarg fields in one scalar round
@@ -182,7 +194,17 @@
     f32x4_t acc[RT][2], accx[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int r = 0; r < RT; ++r) acc[r][0] = acc[r][1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // The row-sum A fragments, made ONCE per wave and behind every request of the prologue (the head of the wave does not grow).  Multi-exponent:
+    // A row 0 = ones, row 1 = the OFF_k pattern of the step's parity, the other rows zero, so D[0][b] = S_1 and D[1][b] = S_off from one product
+    // (the construction of dq_mb_kernel, dqgemm_v2.h); uniform: ones in every row, as before.
+    const typename Q::Consts qc = Q::make_consts();
     const u32x4 ones = {opaque(ACT::ONES), opaque(ACT::ONES), opaque(ACT::ONES), opaque(ACT::ONES)};
+    u32x4 sfr[2] = {ones, ones};
+    if constexpr (!Q::UNIFORM) {
+        const u32x4 zero4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) sfr[k] = j == 0 ? ones : (j == 1 ? Q::off_frag(k, qc) : zero4);
+    }
     // K2_PREFETCH (lab option): the eight ds_read_b128 of chunk i + 1 go out in front of the MFMA steps of chunk i, into the other of two fragment
     // buffers (one wave per SIMD: registers to spare), so their LDS latency hides under arithmetic.  The counted wait for chunk i + 1's slab moves
     // in front of chunk i's arithmetic with them.  Measured on top of K2_AHEAD: profiles/k2h_pipeline.md.
@@ -238,8 +260,8 @@
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
 #pragma unroll
-                        for (int r = 0; r < RT; ++r) acc[r][h] = ACT::mfma(Q::frag(w[i][r], 2 * cb + h), xp[h], acc[r][h]);
-                        accx[h] = ACT::mfma(ones, xp[h], accx[h]);
+                        for (int r = 0; r < RT; ++r) acc[r][h] = ACT::mfma(Q::frag(w[i][r], 2 * cb + h, qc), xp[h], acc[r][h]);
+                        accx[h] = ACT::mfma(sfr[h], xp[h], accx[h]);
                     }
                 });
             } else {
@@ -278,8 +300,8 @@
                 if (NXT < NCH && !((t & 1) && HALF)) dma(NXT, t);    // K2_AHEAD: one request per MFMA step
 #endif
 #pragma unroll
-                for (int r = 0; r < RT; ++r) acc[r][t & 1] = ACT::mfma(Q::frag(w[i][r], t), xf[t], acc[r][t & 1]);
-                accx[t & 1] = ACT::mfma(ones, xf[t], accx[t & 1]);   // row sums of x on the matrix pipe: D[.][b] = sum_k x[b,k]
+                for (int r = 0; r < RT; ++r) acc[r][t & 1] = ACT::mfma(Q::frag(w[i][r], t, qc), xf[t], acc[r][t & 1]);
+                accx[t & 1] = ACT::mfma(sfr[t & 1], xf[t], accx[t & 1]);   // row sums of x on the matrix pipe: D[0][b] = S_1, D[1][b] = S_off
             }
             }
         }
@@ -288,14 +310,17 @@
 
     // ---- meet: the NW k-partials of every tile ---------------------------------------------------------------------------
     {
-        float *p = reinterpret_cast<float *>(myreg);                  // [RT][4][64] accumulator components, then [16] row sums
+        float *p = reinterpret_cast<float *>(myreg);                  // [RT][4][64] accumulator components, then [16] S_1 and [16] S_off
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
             const f32x4_t a = acc[r][0] + acc[r][1];
             p[r * 256 + lane] = a[0]; p[r * 256 + 64 + lane] = a[1];
             p[r * 256 + 128 + lane] = a[2]; p[r * 256 + 192 + lane] = a[3];
         }
-        if (lane < 16) p[RT * 256 + lane] = accx[0][0] + accx[1][0];
+        if (lane < 16) {                                              // lanes 0..15 hold D rows 0..3 of batch column `lane`
+            p[RT * 256 + lane] = accx[0][0] + accx[1][0];
+            if constexpr (!Q::UNIFORM) p[RT * 256 + 16 + lane] = accx[0][1] + accx[1][1];
+        }
     }
     K2_STAMP(5);
     __syncthreads();
@@ -309,19 +334,20 @@
         const int r2 = u >> 2, q = u & 3;
         const int b = 4 * q + (lane >> 4), wr = lane & 15;
         const int src = r2 * 256 + (wr & 3) * 64 + b + 16 * (wr >> 2);
-        float a = 0.f, xsum = 0.f;
+        float a = 0.f, xsum = 0.f, xoff = 0.f;
         // K2_TAIL: hipcc read the row sums, waited lgkmcnt(0), and only then issued the reads of the partials -- two LDS latencies in series on
-        // the tail of every launch.  All 2 NW reads go out, the scheduler may move nothing across the barrier, and the sums (in the same order:
+        // the tail of every launch.  All 2 NW (multi-exponent: 3 NW) reads go out, the scheduler may move nothing across the barrier, and the sums (in the same order:
         // the arithmetic does not move) wait behind it.  -DK2_TAIL=0 (lab builds): no barrier -- hipcc's own order, as measured before.
 #ifndef K2_TAIL
 #define K2_TAIL 1
 #endif
-        float pa[NW], px[NW];
+        float pa[NW], px[NW], po[NW];
 #pragma unroll
         for (int v = 0; v < NW; ++v) {
             const float *p = reinterpret_cast<const float *>(smem + v * (NCH * XB));
             pa[v] = p[src];
             px[v] = p[RT * 256 + b];
+            if constexpr (!Q::UNIFORM) po[v] = p[RT * 256 + 16 + b];
         }
 #if K2_TAIL && defined(__HIP_DEVICE_COMPILE__)
         __builtin_amdgcn_sched_barrier(0);
@@ -330,6 +356,7 @@
         for (int v = 0; v < NW; ++v) {
             a += pa[v];
             xsum += px[v];
+            if constexpr (!Q::UNIFORM) xoff += po[v];
         }
         const int64_t row = (int64_t)(rt0 + r2) * 16 + wr;
         if (b < e.bs) {
@@ -339,8 +366,14 @@
                 e_bi = e.bias ? e.bias[row] : 0.f;
             }
             const float alpha = e.qfn == QUIPAMD_QFN_B ? e_sc * e.two_over_maxq : e_sc;
-            const float c0 = e.qfn == QUIPAMD_QFN_B ? Q::OFF + 0.5f * (float)e.maxq : Q::OFF + e_zr;
-            const float val = alpha * (a - c0 * xsum) + e_bi;
+            float val;
+            if constexpr (Q::UNIFORM) {
+                const float c0 = e.qfn == QUIPAMD_QFN_B ? Q::OFF + 0.5f * (float)e.maxq : Q::OFF + e_zr;
+                val = alpha * (a - c0 * xsum) + e_bi;
+            } else {                                                  // sum_k q x = a - S_off; z = maxq / 2 (qfn b) or zero[row] (qfn a)
+                const float z = e.qfn == QUIPAMD_QFN_B ? 0.5f * (float)e.maxq : e_zr;
+                val = alpha * ((a - xoff) - z * xsum) + e_bi;
+            }
             const int64_t o = (int64_t)b * e.m + row;
             if (e.y_f32) ((float *)e.y)[o] = e.accumulate ? ((float *)e.y)[o] + val : val;
             else ((uint16_t *)e.y)[o] = e.y_f16 ? f32_to_f16_bits(val) : f32_to_bf16_bits(val);

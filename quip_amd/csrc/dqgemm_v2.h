@@ -113,6 +113,12 @@ struct K2Args {
 #ifndef K2_FLAT_ARGS
 #define K2_FLAT_ARGS 1
 #endif
+// K2_H_UNIFORM (lab builds, scripts/k2lab.hip; default 0): 1 = the 4 waves x 4 chunks forms of dq_h_kernel / dq_hg_kernel and dq_hr_kernel
+// dequantise 2-bit codes with the uniform-offset form (16 VALU per packed dword, one row sum) like every other form, instead of the
+// multi-exponent one -- see dq_h_body.inc.
+#ifndef K2_H_UNIFORM
+#define K2_H_UNIFORM 0
+#endif
 #if K2_FLAT_ARGS
 // The pointers travel as 64-bit integers and the scalars behind them as ONE struct: eight arguments, none of pointer type.  Measured
 // (profiles/k2h_head.md, section 5): as fifteen arguments, six of them typed pointers, hipLaunchKernel alone took 4.03 us against 3.71 for
@@ -176,12 +182,17 @@ __global__ __launch_bounds__(64 * NW) void dq_hg_kernel(K2GArgs G)
 template <int BITS, class ACT, int NW, int NCH>
 __global__ __launch_bounds__(64 * NW) void dq_hr_kernel(K2Args A)
 {
-    typedef DeqT<BITS, ACT> Q;
+#if K2_H_UNIFORM
+    typedef DeqUni<BITS, ACT> Q;
+#else
+    typedef DeqSel<BITS, ACT> Q;                                        // the dequantiser, the row-sum fragments and the epilogue of dq_h_body.inc
+#endif
+    constexpr int PARK = 1024 + (Q::UNIFORM ? 64 : 128);                // a wave's partials, then its row sums (16 S_1, 16 S_off)
     constexpr int KC = Q::KC, NT = Q::NT;
     static_assert(BITS == 2 && NT == 8 && KC == 256, "2-bit tiles: 256 columns, 8 MFMA steps");
     static_assert(4 + NCH * NT <= 63, "vmcnt range");
     constexpr int NLD = NCH * NT;                                        // x loads of a wave, behind its NCH weight loads
-    extern __shared__ __attribute__((aligned(16))) char smem[];         // [NW][1024 + 64]: the k-partials of the tile, then 16 row sums
+    extern __shared__ __attribute__((aligned(16))) char smem[];         // [NW][PARK]: the k-partials of the tile, then the row sums
     const EpiArgs &e = A.e;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -189,7 +200,7 @@ __global__ __launch_bounds__(64 * NW) void dq_hr_kernel(K2Args A)
     const int j = lane & 15, g = lane >> 4;
     const uint32_t nkc = (uint32_t)(NW * NCH);
     const uint32_t rt0 = blockIdx.x;
-    char *myreg = smem + wave * (1024 + 64);
+    char *myreg = smem + wave * PARK;
 
     float e_sc = 0.f, e_zr = 0.f, e_bi = 0.f;                             // reducer role q = wave: its epilogue parameters, requested now
     {
@@ -213,7 +224,14 @@ __global__ __launch_bounds__(64 * NW) void dq_hr_kernel(K2Args A)
     });
     K2_STAMP(1);
     f32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, accx[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    const typename Q::Consts qc = Q::make_consts();
     const u32x4 ones = {opaque(ACT::ONES), opaque(ACT::ONES), opaque(ACT::ONES), opaque(ACT::ONES)};
+    u32x4 sfr[2] = {ones, ones};                                          // A row 0 = ones, row 1 = the OFF_k pattern, other rows zero (dq_h_body.inc)
+    if constexpr (!Q::UNIFORM) {
+        const u32x4 zero4 = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) sfr[k] = j == 0 ? ones : (j == 1 ? Q::off_frag(k, qc) : zero4);
+    }
     static_for<NLD>([&](auto IT) {
         constexpr int i = decltype(IT)::value / NT, t = decltype(IT)::value % NT;
         // memory returns in order: behind this wait the NCH weight tiles and the fragments up to (i, t) have landed
@@ -221,8 +239,8 @@ __global__ __launch_bounds__(64 * NW) void dq_hr_kernel(K2Args A)
         asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wi), "+v"(xi) : "n"(NLD - 1 - (i * NT + t)) : "memory");
         if constexpr (i == 0 && t == 0) K2_STAMP(2);
         if constexpr (i == NCH - 1 && t == NT - 1) K2_STAMP(3);
-        acc[t & 1] = ACT::mfma(Q::frag(wi, t), xi, acc[t & 1]);
-        accx[t & 1] = ACT::mfma(ones, xi, accx[t & 1]);                   // row sums of x on the matrix pipe: D[.][b] = sum_k x[b,k]
+        acc[t & 1] = ACT::mfma(Q::frag(wi, t, qc), xi, acc[t & 1]);
+        accx[t & 1] = ACT::mfma(sfr[t & 1], xi, accx[t & 1]);             // row sums of x on the matrix pipe: D[0][b] = S_1, D[1][b] = S_off
     });
     K2_STAMP(4);
     // ---- meet: the NW k-partials of the tile (as dq_h_body.inc, one row tile) ----------------------------------------------------------
@@ -230,7 +248,10 @@ __global__ __launch_bounds__(64 * NW) void dq_hr_kernel(K2Args A)
         float *p = reinterpret_cast<float *>(myreg);
         const f32x4_t a = acc[0] + acc[1];
         p[lane] = a[0]; p[64 + lane] = a[1]; p[128 + lane] = a[2]; p[192 + lane] = a[3];
-        if (lane < 16) p[256 + lane] = accx[0][0] + accx[1][0];
+        if (lane < 16) {
+            p[256 + lane] = accx[0][0] + accx[1][0];
+            if constexpr (!Q::UNIFORM) p[256 + 16 + lane] = accx[0][1] + accx[1][1];
+        }
     }
     K2_STAMP(5);
     __syncthreads();
@@ -240,18 +261,25 @@ __global__ __launch_bounds__(64 * NW) void dq_hr_kernel(K2Args A)
     for (int u = wave; u < 4; u += NW) {                                 // role u: batch rows 4u .. 4u + 3 x the 16 weight rows
         const int b = 4 * u + (lane >> 4), wr = lane & 15;
         const int src = (wr & 3) * 64 + b + 16 * (wr >> 2);
-        float a = 0.f, xsum = 0.f;
+        float a = 0.f, xsum = 0.f, xoff = 0.f;
 #pragma unroll
         for (int v = 0; v < NW; ++v) {
-            const float *p = reinterpret_cast<const float *>(smem + v * (1024 + 64));
+            const float *p = reinterpret_cast<const float *>(smem + v * PARK);
             a += p[src];
             xsum += p[256 + b];
+            if constexpr (!Q::UNIFORM) xoff += p[256 + 16 + b];
         }
         const int64_t row = (int64_t)rt0 * 16 + wr;
         if (b < e.bs) {
             const float alpha = e.qfn == QUIPAMD_QFN_B ? e_sc * e.two_over_maxq : e_sc;
-            const float c0 = e.qfn == QUIPAMD_QFN_B ? Q::OFF + 0.5f * (float)e.maxq : Q::OFF + e_zr;
-            const float val = alpha * (a - c0 * xsum) + e_bi;
+            float val;
+            if constexpr (Q::UNIFORM) {
+                const float c0 = e.qfn == QUIPAMD_QFN_B ? Q::OFF + 0.5f * (float)e.maxq : Q::OFF + e_zr;
+                val = alpha * (a - c0 * xsum) + e_bi;
+            } else {
+                const float z = e.qfn == QUIPAMD_QFN_B ? 0.5f * (float)e.maxq : e_zr;
+                val = alpha * ((a - xoff) - z * xsum) + e_bi;
+            }
             const int64_t o = (int64_t)b * e.m + row;
             if (e.y_f32) ((float *)e.y)[o] = e.accumulate ? ((float *)e.y)[o] + val : val;
             else ((uint16_t *)e.y)[o] = e.y_f16 ? f32_to_f16_bits(val) : f32_to_bf16_bits(val);
@@ -265,7 +293,7 @@ int launch_hr(const K2Args &A, hipStream_t s)
 {
     static_assert(NW == 4, "four reducer roles, one per wave");
     auto kern = dq_hr_kernel<BITS, ACT, NW, NCH>;
-    kern<<<dim3((unsigned)(A.e.m / 16)), 64 * NW, NW * (1024 + 64), s>>>(A);
+    kern<<<dim3((unsigned)(A.e.m / 16)), 64 * NW, NW * (1024 + 128), s>>>(A);      // PARK of the kernel at its largest
     QA_LAUNCH_CHECK("quipamd_dequant_gemm(hr)");
     return QUIPAMD_OK;
 }

@@ -4,6 +4,8 @@
 //        + the flags build() gives csrc/dqgemm_v2.hip (`python -c "import __graft_entry__ as g; print(*g.hip_flags('dqgemm_v2.hip'))"`: today
 //        -mllvm -amdgpu-kernarg-preload-count=16) -- without them dq_h_kernel is NOT the shipped kernel: preload length 0, its arguments read in
 //        a scalar round trip in front of the weight tiles (launch_h passes them through K2_H_PASS either way: csrc/dqgemm_v2.h)
+//        A/B switches of dq_h_kernel (defaults in csrc/dqgemm_v2.h / dq_h_body.inc): -DK2_AHEAD=n, -DK2_HEAD=0, -DK2_H_UNIFORM=1 (the
+//        uniform-offset 2-bit dequantiser instead of the multi-exponent one: profiles/k2h_me.md)
 // run:   build/k2lab <mode> [m d bs bits act]     mode: null | h | s | mb | old
 #include "../quip_amd/csrc/capi.hip"
 #include "../quip_amd/csrc/dqgemm.hip"
