@@ -1,5 +1,5 @@
 """ctypes loader for libquip_amd.so (the C ABI of include/quip_amd.h, include/quip_amd_prefill.h, include/quip_amd_sample.h,
-include/quip_amd_generate.h and include/quip_amd_score.h).
+include/quip_amd_generate.h, include/quip_amd_score.h and include/quip_amd_groupwise.h).
 
 The product path has no CPU fallback: if the shared library is missing or a symbol is absent, importing the
 ops fails loudly here.  Build it with `python __graft_entry__.py` (hipcc --offload-arch=gfx950).
@@ -126,6 +126,12 @@ SCORE_SIGNATURES = {
     "quipamd_head_score": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
 }
 
+# the group-wise dequant-GEMM: include/quip_amd_groupwise.h, a sixth table for the same reason; tests/test_groupwise_host.py checks this table
+# against that header and tests/test_gpu_groupwise_contract.py runs every launching name of it under a guard arena
+GROUPWISE_SIGNATURES = {
+    "quipamd_dequant_gemm_groupwise": [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp],
+}
+
 _lib = None
 
 
@@ -166,6 +172,13 @@ def load():
             raise QuipAmdError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.argtypes = argtypes
         fn.restype = c_i64 if name.endswith("_workspace_bytes") else c_int
+    for name, argtypes in GROUPWISE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise QuipAmdError(f"{LIB_PATH} does not export {name}; rebuild it") from e
+        fn.argtypes = argtypes
+        fn.restype = c_int
     _lib = lib
     return lib
 

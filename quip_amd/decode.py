@@ -42,11 +42,31 @@ OPERAND_PREFETCH = False   # True: v3 launches carry 8 spare workgroups that pul
 
 
 # ------------------------------------------------------------------------------------------------ packed layers out of a driver run
+def _groupwise_unpackable(m):
+    """why a method that kept codes beside group tables (GPTQ with --groupsize) cannot become a group-wise QuantLinear, or None when it
+    can (also for every method without groups)"""
+    gs = getattr(m, 'group_scale', None)
+    if gs is None or getattr(m, 'group_zero', None) is None:
+        return None
+    rows, cols = m.codes.shape
+    G = cols // max(gs.shape[1], 1)
+    bits = int(torch.log2(m.quantizer.maxq.float() + 1).round().item())
+    if G not in ops.GROUPSIZES:
+        return f"groupsize {G}: the group-wise dequant-GEMM serves 32, 64 and 128"
+    if bits not in (2, 3, 4):
+        return f"{bits} bits: packed layers hold 2, 3 or 4"
+    if rows % 16 or cols % ops.stream_chunk(bits):
+        return f"the STREAM layout needs out_features % 16 == 0 and in_features % {ops.stream_chunk(bits)} == 0"
+    return None
+
+
 class collect_packed:
     """context manager: while it is active every `QuantMethod.free()` (the last call the reference's drivers make on a method,
     opt.py:166, llama.py:150) first turns the method's integer state into a packed `QuantLinear` (QuantLinear.from_method: codes,
     grid, rescale vector, operators -- what the reference throws away, method.py:223-225).  Methods without integer codes
-    (Nearest, GPTQ's general path) are skipped and stay dense.  `install(model)` swaps the collected layers into the model.
+    (Nearest, GPTQ's column walk) are skipped and stay dense.  GPTQ with `--groupsize` 32 / 64 / 128 yields a group-wise QuantLinear (one
+    (scale, zero) per row and group, csrc/dqgemm_gw.hip); groups of 16, or a shape the STREAM layout cannot hold, stay dense with one
+    printed line.  `install(model)` swaps the collected layers into the model.
     native3: layers quantised to 3 bits are packed in the STREAM3 layout (3 bits per weight) instead of the 4-bit container; ignored
     for every other width."""
 
@@ -60,7 +80,11 @@ class collect_packed:
 
         def free(m):
             if getattr(m, 'codes', None) is not None and isinstance(m.layer, nn.Linear):
-                got.append((m.layer, QuantLinear.from_method(m, m.layer, native3=native3)))
+                why = _groupwise_unpackable(m)
+                if why is None:
+                    got.append((m.layer, QuantLinear.from_method(m, m.layer, native3=native3)))
+                else:                                     # one line, no exception in the middle of a driver run: the layer stays dense
+                    print(f"collect_packed: a {m.codes.shape[0]} x {m.codes.shape[1]} layer quantised with groups stays dense ({why})")
                 m.codes = None
             return orig(m)
         _method.QuantMethod.free = free
@@ -516,9 +540,17 @@ def set_mode(dec, mode):
     dec.mode = mode
 
 
+def groupwise_layers(dec):
+    """[(dotted name, layer)] of the decoder's group-wise packed layers: they run through their own forward (modes plain / fused), never
+    through the fused decode launches, which read one scale per tensor"""
+    return [(n, l) for n, l in dec.named_modules() if isinstance(l, QuantLinear) and l.groupwise]
+
+
 def best_mode(dec, bs, dtype, max_len=None):
     """the fastest launch sequence the decoder's layers allow (module docstring) for `bs` sequences over caches of max_len positions"""
     if dec.packed():
+        if groupwise_layers(dec):
+            return "fused"
         if dtype == torch.float16 and dec.v3_ok(bs, max_len):
             return "v3_head" if dec.head_ok(bs) else "v3"
         return "fused"
@@ -670,6 +702,11 @@ class DecodeEngine:
             max_len = min(max_len, decoder.cos.shape[0])
         self.dev, self.dtype, self.bs, self.max_len = w.device, w.dtype, bs, max_len
         self.mode = best_mode(decoder, bs, self.dtype, max_len) if mode == "auto" else mode
+        if self.mode in ("v3", "v3_head"):
+            gw = groupwise_layers(decoder)
+            if gw:
+                raise ValueError(f"DecodeEngine: mode {self.mode!r} runs the fused decode launches, which read one scale per tensor, but layer "
+                                 f"{gw[0][0]!r} holds a group-wise grid (groupsize {gw[0][1].groupsize}); use mode 'auto', 'fused' or 'plain'")
         set_mode(decoder, self.mode)
         hd = decoder.h // decoder.heads
         kv_heads = decoder.kv_heads

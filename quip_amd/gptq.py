@@ -6,7 +6,8 @@ feedback modes (include/quip_amd.h), fed by ops.gptq_feedback (flip + K8 Cholesk
 matrix pipe instead of gptq.py:51-54's three rocSOLVER factorisations):
   * ops.gptq_round         qfn a, groupsize -1: grid coordinates, codes kept for packing;
   * ops.gptq_round_groups  groupsize 16/32/64/128 (the group quantisers are found inside the kernel from the block-lazy W,
-                           like gptq.py:72-75) and qfn c, in weight units with the reference's quantiser formula;
+                           like gptq.py:72-75) and qfn c, in weight units with the reference's quantiser formula; with groups the codes
+                           and the [m, d / groupsize] tables are kept for packing (a group-wise QuantLinear);
 (nn.Linear is the only layer kind the reference's own preproc / error_compute survive: method.py:187 and :232 index a
 Conv1D / Conv2d weight as if it were [out, in].)
   * ops.gptq_round_qfnb    qfn b (`--incoh_processing`): Quantizer.quantize recomputes ONE scale from all rows of every updated column
@@ -125,10 +126,12 @@ class GPTQ(QuantMethod):
         # the kernel's lazy block is 128 columns wide: with another blocksize the groups would see a different W (gptq.py:72-75)
         if groupsize not in (16, 32, 64, 128) or d % groupsize or not qz.perchannel or qz.mse or blocksize != 128:
             return None
-        Q, scale, zero = ops.gptq_round_groups(W.float().contiguous(), None, bits, groupsize, qz.sym, qz.qfn, FT=ops.gptq_feedback(H.float()))
+        Q, scale, zero, codes = ops.gptq_round_groups(W.float().contiguous(), None, bits, groupsize, qz.sym, qz.qfn, FT=ops.gptq_feedback(H.float()),
+                                                      return_codes=True)
         # the reference leaves the LAST group's quantiser in self.quantizer (gptq.py:72-75)
         qz.scale, qz.zero = scale[:, -1:].clone(), zero[:, -1:].clone()
-        self.group_scale, self.group_zero = scale, zero
+        # the codes beside the [m, d / groupsize] tables: what QuantLinear.from_method packs into a group-wise layer (decode.collect_packed)
+        self.codes, self.group_scale, self.group_zero = codes, scale, zero
         return Q.to(W.dtype)
 
 

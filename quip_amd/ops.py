@@ -256,6 +256,45 @@ def dequant_gemm(x, qweight, bits, qfn, scale, zero, bias, out=None, out_dtype=N
     return out
 
 
+GROUPSIZES = (32, 64, 128)      # group-wise grids the fused GEMM serves (csrc/dqgemm_gw.hip): a group is whole 32-deep MFMA steps
+
+
+def group_tables(scale, zero):
+    """the [m, d/G] pair gptq_round_groups returns -> the contiguous GROUP-MAJOR fp32 pair [d/G, m] dequant_gemm_groupwise reads (the four
+    consecutive output rows a lane owns are one 16-byte load)"""
+    assert scale.dim() == 2 and scale.shape == zero.shape, "scale and zero must both be [m, d/G]"
+    return (scale.to(torch.float32).t().contiguous(), zero.to(torch.float32).t().contiguous())
+
+
+def dequant_gemm_groupwise(x, qweight, bits, groupsize, gscale, gzero, bias=None, out=None, out_dtype=None, m=None):
+    """y[bs, m] = bias + sum_g gscale[g] * sum_{k in group g} (code - gzero[g]) * x  (include/quip_amd_groupwise.h, csrc/dqgemm_gw.hip): one
+    (scale, zero) per row and per group of `groupsize` (32 / 64 / 128) consecutive input columns.  qweight: STREAM layout; gscale, gzero:
+    fp32 GROUP-MAJOR [d/G, m] (group_tables); x: fp16 or bf16 [bs, d]; y: x's dtype (default), fp32, fp16 or bf16."""
+    _need_gpu(x, qweight, gscale, gzero, out)
+    assert x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16), "x must be bf16 or fp16"
+    x = x.contiguous()
+    bs, d = x.shape
+    if m is None:
+        m = qweight.numel() * 32 // container_bits(bits) // d
+    if groupsize not in GROUPSIZES or d % groupsize:
+        raise ValueError(f"dequant_gemm_groupwise: groupsize {groupsize} must be 32, 64 or 128 and divide {d}")
+    for name, t in (("gscale", gscale), ("gzero", gzero)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (d // groupsize, m) or not t.is_contiguous():
+            raise ValueError(f"dequant_gemm_groupwise: {name} must be contiguous fp32 [d/G, m] = [{d // groupsize}, {m}] (group-major; "
+                             f"ops.group_tables), got {t.dtype} {tuple(t.shape)}")
+    if qweight.numel() != packed_words(bits, LAYOUT_STREAM, m, d):
+        raise ValueError(f"dequant_gemm_groupwise: qweight has {qweight.numel()} words for {m} x {d} at {bits} bits")
+    bias = _f32vec(bias, x.device)
+    if bias is not None and bias.numel() != m:
+        raise ValueError(f"bias has {bias.numel()} values for {m} rows")
+    if out is None:
+        out = torch.empty((bs, m), dtype=out_dtype or x.dtype, device=x.device)
+    assert out.is_contiguous() and out.shape == (bs, m)
+    _lib.call("quipamd_dequant_gemm_groupwise", _p(x), _dtype(x), _p(qweight), bits, int(groupsize), _p(gscale), _p(gzero), _p(bias), _p(out),
+              _dtype(out), bs, m, d, _stream())
+    return out
+
+
 def dequant_gemm_grouped(xs, qweights, bits, qfn, scales, zeros, outs, m, layout=LAYOUT_STREAM):
     """ngroups <= 4 problems of identical shape (and layout) in one call: xs[i] [bs,d] bf16 / fp16, outs[i] [bs,m] (fp32 or x's dtype)."""
     n = len(xs)

@@ -167,9 +167,22 @@ class QuantLinear(nn.Module):
 
     where What2 = dequant(codes) lives in the projected basis.  forward() accepts any batch shape."""
 
-    def __init__(self, infeatures, outfeatures, bits=2, qfn='b', native3=False):
+    def __init__(self, infeatures, outfeatures, bits=2, qfn='b', native3=False, groupsize=-1):
         super().__init__()
         assert bits in (2, 3, 4)                  # 3-bit codes (--wbits 3) are stored in the 4-bit container, or with native3 at 3 bits
+        groupsize = -1 if groupsize is None or int(groupsize) <= 0 else int(groupsize)
+        if groupsize > 0:
+            # a group-wise grid (--groupsize): one (scale, zero) per row and per `groupsize` input columns, served by csrc/dqgemm_gw.hip only
+            if groupsize not in ops.GROUPSIZES or infeatures % groupsize:
+                raise ValueError(f"a group-wise QuantLinear needs groupsize 32, 64 or 128 dividing infeatures (groupsize={groupsize}, "
+                                 f"{infeatures} -> {outfeatures})")
+            if qfn == 'b':
+                raise ValueError("a group-wise QuantLinear has a (scale, zero) grid per group: qfn 'b' (one scale per tensor) has no groups")
+            if native3:
+                raise ValueError("a group-wise QuantLinear keeps its codes in the STREAM container: native3 (STREAM3) has no group-wise kernel")
+            if outfeatures % 16 or infeatures % ops.stream_chunk(bits):
+                raise ValueError(f"a group-wise QuantLinear needs outfeatures % 16 == 0 and infeatures % {ops.stream_chunk(bits)} == 0 "
+                                 f"({infeatures} -> {outfeatures} at {bits} bits)")
         if native3 and (bits != 3 or infeatures % 256 != 0 or outfeatures % 16 != 0):
             raise ValueError(f"native3 is the STREAM3 layout of 3-bit codes: needs bits == 3, infeatures % 256 == 0 and outfeatures % 16 == 0 "
                              f"(bits={bits}, {infeatures} -> {outfeatures})")
@@ -181,12 +194,26 @@ class QuantLinear(nn.Module):
         self.register_buffer('zeros', torch.zeros(outfeatures) if qfn != 'b' else None)
         self.register_buffer('bias', None)
         self.register_buffer('inv_scaleWH', None)
+        self.groupsize = groupsize
+        ng = infeatures // groupsize if groupsize > 0 else 0
+        self.register_buffer('gscales', torch.zeros(ng, outfeatures) if ng else None)     # group-major [d/G, m] (ops.group_tables)
+        self.register_buffer('gzeros', torch.zeros(ng, outfeatures) if ng else None)
         self.U = None     # ops.OrthoOp over out features
         self.V = None     # ops.OrthoOp over in features
         self._drop_derived()
 
-    _F32_BUFFERS = ('scales', 'zeros', 'bias', 'inv_scaleWH')
+    _F32_BUFFERS = ('scales', 'zeros', 'bias', 'inv_scaleWH', 'gscales', 'gzeros')
     layout = ops.LAYOUT_STREAM        # (class default: a module pickled before the STREAM3 layout existed holds the container)
+    groupsize = -1                    # (class default: a module pickled before group-wise grids existed has none)
+
+    @property
+    def groupwise(self):
+        return self.groupsize > 0
+
+    def _no_groups(self, what):
+        if self.groupwise:
+            raise ValueError(f"QuantLinear.{what}: this layer holds a group-wise grid (groupsize={self.groupsize}, {self.infeatures} -> "
+                             f"{self.outfeatures}); the fused decode launches and STREAM3 read one scale per tensor -- it runs through forward()")
 
     def _apply(self, fn, recurse=True):
         """model.half() / .to(dtype) must not narrow the grid parameters: the kernels read them as float32 (and fp16 could
@@ -219,12 +246,23 @@ class QuantLinear(nn.Module):
         """codes uint8 [out,in] on the GPU; scale float[1] (qfn b) or [out] (qfn a); U/V reference-style
         (B, p_in, p_out) tuples or ops.OrthoOp."""
         dev = codes.device
+        if self.groupwise:
+            ng = self.infeatures // self.groupsize
+            if zero is None or tuple(scale.shape) != (self.outfeatures, ng) or tuple(zero.shape) != (self.outfeatures, ng):
+                raise ValueError(f"a group-wise QuantLinear packs scale and zero of shape [m, d/G] = [{self.outfeatures}, {ng}], got "
+                                 f"{tuple(scale.shape)} and {None if zero is None else tuple(zero.shape)}")
+            if tuple(codes.shape) != (self.outfeatures, self.infeatures):
+                raise ValueError(f"codes must be [{self.outfeatures}, {self.infeatures}], got {tuple(codes.shape)}")
         # what the decode launches derive from the packed state (decode_qweight, bias16, the layer-pair tables) is rebuilt on next use;
         # tables other layers keep about THIS one are keyed by its generation
         self._drop_derived()
         self.qweight = ops.pack(codes, self.bits, self.layout)
-        self.scales = scale.to(dev, torch.float32).reshape(-1).clone()
-        self.zeros = None if zero is None else zero.to(dev, torch.float32).reshape(-1).clone()
+        if self.groupwise:
+            self.gscales, self.gzeros = ops.group_tables(scale.to(dev), zero.to(dev))
+            self.scales, self.zeros = torch.zeros(0, device=dev), torch.zeros(0, device=dev)      # no per-row grid
+        else:
+            self.scales = scale.to(dev, torch.float32).reshape(-1).clone()
+            self.zeros = None if zero is None else zero.to(dev, torch.float32).reshape(-1).clone()
         self.bias = None if bias is None else bias.detach().to(dev, torch.float32).clone()
         self.inv_scaleWH = None if scaleWH is None else (1.0 / scaleWH.to(dev, torch.float32))
         self.U = U if (U is None or isinstance(U, ops.OrthoOp)) else ops.OrthoOp(U, dev)
@@ -250,6 +288,7 @@ class QuantLinear(nn.Module):
     def to_native3(self):
         """convert a packed 3-bit layer from the 4-bit container to STREAM3 in place, on the device (unpack -> pack): 25 % fewer resident
         bytes, the same codes.  Returns self; a layer that is native already is left alone."""
+        self._no_groups("to_native3")
         if self.native3:
             return self
         if self.bits != 3 or self.infeatures % 256 != 0 or self.outfeatures % 16 != 0:
@@ -271,6 +310,7 @@ class QuantLinear(nn.Module):
     def decode_only(self):
         """keep ONLY the decode-order codes (the fused decode launches read nothing else): frees the natural-order STREAM words, after which
         forward() / the K3-side stages of this layer raise.  For serving from the fused engine at 2 bits per weight instead of 4."""
+        self._no_groups("decode_only")
         self.decode_qweight()
         self.qweight = torch.empty(0, dtype=torch.int32, device=self.qweight.device)
         return self
@@ -284,6 +324,15 @@ class QuantLinear(nn.Module):
         codes = method.codes
         bits = int(torch.log2(method.quantizer.maxq.float() + 1).round().item())
         qfn = method.quantizer.qfn if method.quantizer.qfn in ('a', 'b') else 'a'
+        gs, gz = getattr(method, 'group_scale', None), getattr(method, 'group_zero', None)
+        if gs is not None and gz is not None:
+            # a group-wise grid (GPTQ with --groupsize): [m, d/G] tables instead of the quantiser's per-row pair
+            ql = cls(codes.shape[1], codes.shape[0], bits=bits, qfn='a', groupsize=codes.shape[1] // gs.shape[1])
+            U = getattr(method, '_U', None) if getattr(method, 'preproc_proj', False) else None
+            V = getattr(method, '_V', None) if getattr(method, 'preproc_proj', False) else None
+            sWH = method.scaleWH if getattr(method, 'preproc_rescale', False) else None
+            bias = None if getattr(layer, 'bias', None) is None else layer.bias.data
+            return ql.pack(codes, gs, gz, bias=bias, scaleWH=sWH, U=U, V=V)
         # native3: the STREAM3 layout where the method quantised to 3 bits and the shape allows it; ignored otherwise
         native3 = bool(native3) and bits == 3 and codes.shape[1] % 256 == 0 and codes.shape[0] % 16 == 0
         ql = cls(codes.shape[1], codes.shape[0], bits=bits, qfn=qfn, native3=native3)
@@ -297,6 +346,7 @@ class QuantLinear(nn.Module):
     def decode_qweight(self):
         """the codes as the fused decode launches read them (include/quip_amd.h "permutations folded into the packing"): rows in ZT order
         of U, columns in image order of V -- built once (unpack, index, pack on the device) and kept beside `qweight`"""
+        self._no_groups("decode_qweight")
         qd = self.__dict__.get('_qweight_d')
         if qd is None or qd.device != self.qweight.device:
             if self.qweight.numel() == 0:
@@ -336,14 +386,18 @@ class QuantLinear(nn.Module):
         return {"infeatures": self.infeatures, "outfeatures": self.outfeatures, "bits": self.bits, "qfn": self.qfn,
                 "layout": self.layout, "qweight": cpu(self.qweight), "scales": cpu(self.scales), "zeros": cpu(self.zeros), "bias": cpu(self.bias),
                 "inv_scaleWH": cpu(self.inv_scaleWH),
-                "U": None if self.U is None else self.U.state(), "V": None if self.V is None else self.V.state()}
+                "U": None if self.U is None else self.U.state(), "V": None if self.V is None else self.V.state(),
+                **({"groupsize": self.groupsize, "gscales": cpu(self.gscales), "gzeros": cpu(self.gzeros)} if self.groupwise else {})}
 
     @classmethod
     def from_packed_state(cls, st, device):
         # a record without "layout" was written before STREAM3 existed: the container
+        # ... and one without "groupsize" before group-wise grids did: today's per-row / per-tensor layer
         ql = cls(st["infeatures"], st["outfeatures"], bits=st["bits"], qfn=st["qfn"],
-                 native3=st.get("layout", ops.LAYOUT_STREAM) == ops.LAYOUT_STREAM3)
+                 native3=st.get("layout", ops.LAYOUT_STREAM) == ops.LAYOUT_STREAM3, groupsize=st.get("groupsize", -1))
         dev = lambda t: None if t is None else t.to(device)
+        if ql.groupwise:
+            ql.gscales, ql.gzeros = dev(st["gscales"]), dev(st["gzeros"])
         ql.qweight, ql.scales, ql.zeros = dev(st["qweight"]), dev(st["scales"]), dev(st["zeros"])
         ql.bias, ql.inv_scaleWH = dev(st["bias"]), dev(st["inv_scaleWH"])
         ql.U = None if st["U"] is None else ops.OrthoOp(st["U"], device)
@@ -376,7 +430,12 @@ class QuantLinear(nn.Module):
             xt = x2.to(adt)
             if self.inv_scaleWH is not None:
                 xt = (x2.float() * self.inv_scaleWH).to(adt)
-        if self.U is None:
+        if self.groupwise:
+            y = ops.dequant_gemm_groupwise(xt, self.qweight, self.bits, self.groupsize, self.gscales, self.gzeros,
+                                           self.bias if self.U is None else None, out_dtype=torch.float32, m=self.outfeatures)
+            if self.U is not None:
+                y = self.U.apply_rows(y, transpose=True, out_dtype=x.dtype, bias=self.bias, fast16=few)
+        elif self.U is None:
             y = ops.dequant_gemm(xt, self.qweight, self.bits, self.qfn, self.scales, self.zeros, self.bias,
                                  out_dtype=torch.float32, m=self.outfeatures, layout=self.layout)
         else:
@@ -524,9 +583,14 @@ def _ln_params(ln):
     return (ln.weight, beta, eps)
 
 
+def _gw(ql):
+    """does this layer hold a group-wise grid?  (such a layer never reaches a fused decode launch: they read one scale per tensor)"""
+    return bool(getattr(ql, 'groupwise', False))
+
+
 def _fusable(ql, rows):
     return (ql.U is not None and ql.V is not None and ql.U.small_ok and ql.V.small_ok and rows <= ops.OrthoOp.SMALL_ROWS
-            and ql.qfn == 'b')
+            and ql.qfn == 'b' and not _gw(ql))
 
 
 def _norm(ln, x):
@@ -734,8 +798,9 @@ def fused_ok(qls, rows, x_dtype=torch.float16, prev=None, norm=True, residual=Tr
           and all(q.bits in (2, 3, 4) and q.qfn == 'b' and q.V is not None and q.V.fused_ok and q.scales.numel() == 1 for q in qls)
           and len({(q.infeatures, q.outfeatures, q.V.p, q.V.q, q.bits) for q in qls}) == 1
           and q0.outfeatures % (32 if (q0.V.p, q0.V.q) == (64, 32) else 16) == 0)
+    ok = ok and not any(_gw(q) for q in qls)           # (a group-wise grid is qfn a already; said again for the reader)
     if ok and prev is not None:
-        ok = prev.U is not None and prev.U.fused_ok and (prev.U.p, prev.U.q) == (q0.V.p, q0.V.q)
+        ok = not _gw(prev) and prev.U is not None and prev.U.fused_ok and (prev.U.p, prev.U.q) == (q0.V.p, q0.V.q)
     if ok:
         big = (q0.V.p, q0.V.q) == (128, 64)
         ok = (not norm and (prev is None or not residual)) if big else (prev is None or residual)
@@ -780,7 +845,7 @@ def bigp_tail_ok(ups, down, rows):
     shape of the consumer's activation-side operator, 2-bit qfn-b consumer with one scale, a handful of rows)"""
     V = down.V
     return (1 <= len(ups) <= 2 and rows <= ops.BIGP_MAX_ROWS and V is not None and V.bigp_fold_ok and down.bits in (2, 3, 4) and down.qfn == 'b'
-            and down.scales.numel() == 1 and down.outfeatures % 256 == 0
+            and down.scales.numel() == 1 and down.outfeatures % 256 == 0 and not _gw(down) and not any(_gw(q) for q in ups)
             and all(q.U is not None and q.U.bigp_fold_ok and (q.U.p, q.U.q) == (V.p, V.q) for q in ups))
 
 
@@ -854,7 +919,8 @@ def fused_u_only(ql, y, residual=None, relu=False):
 
 def fused_head_ok(ql, rows, ln):
     """can `fused_head` finish a decode step behind packed layer `ql`?  (csrc/decode_head.hip: U 64 x 32 / 64 x 64, a norm, <= 4 rows)"""
-    return (ql.U is not None and ql.U.fused_ok and (ql.U.p, ql.U.q) in ((64, 32), (64, 64)) and rows <= ops.FUSED_MAX_ROWS and _ln_params(ln) is not None)
+    return (not _gw(ql) and ql.U is not None and ql.U.fused_ok and (ql.U.p, ql.U.q) in ((64, 32), (64, 64)) and rows <= ops.FUSED_MAX_ROWS
+            and _ln_params(ln) is not None)
 
 
 def fused_head(ql, y, residual, ln, W, logits, part_val=None, part_idx=None, pos_inc=None):
@@ -871,7 +937,7 @@ def fused_attention_ok(qkv, kcache):
     maxlen the launch's LDS holds: ops.decode_attention_fused_max_len)"""
     bs, heads, maxlen, hd = kcache.shape
     shapes = {(q.U.p, q.U.q) for q in qkv if q.U is not None}
-    return (len(qkv) == 3 and all(q.U is not None and q.U.fused_ok for q in qkv) and len(shapes) == 1 and kcache.dtype == torch.float16
+    return (len(qkv) == 3 and all(q.U is not None and q.U.fused_ok and not _gw(q) for q in qkv) and len(shapes) == 1 and kcache.dtype == torch.float16
             and next(iter(shapes)) in (((64, 32),) if hd == 64 else ((64, 64), (64, 32)) if hd == 128 else ())
             and all(q.outfeatures == heads * hd for q in qkv) and maxlen <= ops.decode_attention_fused_max_len(hd, *next(iter(shapes))))
 
